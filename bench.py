@@ -1,6 +1,7 @@
 """Bench: DCT energy map of a 16384^2 RGB frame, N = 8 (BASELINE.json configs[2..3]).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--n 8] [--size 16384] [--weak]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 
 One process per GPU.  With --gpus N > 1 and no launcher around it (WORLD_SIZE
@@ -14,14 +15,27 @@ while the interior rows run, then the halo-dependent rows.  Input resident in
 HBM, output left in HBM.  --weak gives every rank its own size x size band of
 a (N * size) x size frame instead.
 
-Prints ONE JSON line (rank 0).  `value` = Mpx/s over all ranks.  `roofline`
-prices the map kernel (dcte_map<N,RGB>) against the 8 TB/s HBM roof with the
-algorithmic 7 B/px (3 B in + 4 B out), timed by HIP events around each launch
+Prints ONE JSON line (rank 0).  `value` = Mpx/s over all ranks, `ms_per_step`
+= the milliseconds one timed step took.  `roofline` prices the map kernel
+(dcte_map<N,RGB>) against the 8 TB/s HBM roof with the algorithmic 7 B/px
+(3 B in + 4 B out), timed by HIP events around each launch of the timed steps
 on the launch stream (dcte_profile_read); the binding roof is the VALU,
-reported in `valu`.  `cpu_baseline` times the reference's own transforms
-(oracle/_ref, src/fft2d compiled unmodified) on this host's cores over a
-bounded sample of the frame; `host_path` times the plug-in's real call
-(host frame -> dcte_energy_map -> host map, PCIe-inclusive).
+reported in `valu`.
+
+A plain run sets up, warms up, times the K steps and prints that line.
+--dump-outputs DIR writes what the last timed step left in the output map to
+DIR/<name>.npy (float32; frames above the 48 MB budget as a fixed, seeded
+sample of whole rows, the row numbers beside it), so that two builds can be
+compared output for output: the frame is the same from run to run.
+
+--full adds, after the timed region, everything else the bench measures or
+checks: `stress` (the tie-dense line-art frame), `exact` (DCTE_OPT_EXACT),
+`configs_1gpu` (BASELINE configs[1] / configs[4] and a 2048^2 layer),
+`host_path` (the plug-in's real call: host frame -> dcte_energy_map -> host
+map, PCIe-inclusive) and `cpu_baseline` (the reference's own transforms,
+oracle/_ref, src/fft2d compiled unmodified, on this host's cores over a bounded
+sample of the frame); with --gpus N > 1 the bit-exact band check, the halo
+exchange alone and the end-to-end figure (step + band gather).
 """
 import argparse
 import json
@@ -47,6 +61,14 @@ def parse(argv=None):
     ap.add_argument("--size", type=int, default=16384)
     ap.add_argument("--edges", type=float, default=0.3)
     ap.add_argument("--textures", type=float, default=0.7)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's output map to DIR/<name>.npy "
+                         "(float32; a fixed, seeded sample of whole rows when the map is larger "
+                         "than the budget)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run everything else the bench measures or "
+                         "checks (stress frame, exact mode, other configs, host path, CPU baseline; "
+                         "--gpus > 1: band check, halo exchange alone, end-to-end gather)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-rows", type=int, default=0,
                     help="output rows of the CPU-baseline sample (0: sized to ~15 s of CPU work)")
@@ -65,10 +87,11 @@ def parse(argv=None):
                          "(N * size) x size frame")
     ap.add_argument("--check", action="store_true",
                     help="after timing, recompute every band from regenerated rows (no "
-                         "exchange) and require bit-equality (default on for --gpus > 1)")
-    ap.add_argument("--no-check", action="store_true", help="skip that check for --gpus > 1")
+                         "exchange) and require bit-equality (on with --full --gpus > 1)")
+    ap.add_argument("--no-check", action="store_true",
+                    help="--full --gpus > 1: skip that check")
     ap.add_argument("--no-e2e", action="store_true",
-                    help="--gpus > 1: skip the end-to-end figure (step + band gather to rank 0)")
+                    help="--full --gpus > 1: skip the end-to-end figure (step + band gather to rank 0)")
     ap.add_argument("--shared-gpu", action="store_true",
                     help="RCCL rehearsal on a box with fewer GPUs than ranks: the self-launched "
                          "ranks get distinct NCCL_HOSTIDs so RCCL accepts several ranks on one "
@@ -78,7 +101,10 @@ def parse(argv=None):
                     help="no GPU: launch the ranks, split a --size frame into bands and "
                          "exchange the halos over gloo on CPU tensors, check them against "
                          "the global frame (tests/test_bench_launch.py)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 # ------------------------------------------------------------------ launcher
@@ -505,6 +531,34 @@ def pmc_figures(n, W, px_per_rank):
     return out
 
 
+# --dump-outputs: bytes of map written by all ranks together (whole rows)
+DUMP_BUDGET_BYTES = 48 * 1000 * 1000
+
+
+def dump_outputs(directory, out, rank, world):
+    """The timed path's result -- this rank's band of the energy map as the
+    last timed step left it in HBM -- as float32 .npy files: `energy_map.npy`
+    (one rank) or `energy_map_rank<r>.npy`.  A band above this rank's share of
+    DUMP_BUDGET_BYTES is written as a sample of whole rows, drawn once with a
+    fixed seed (the same rows in every run and build), and the rows' numbers
+    within the band go to `<name>_rows.npy` (float64, exact)."""
+    import numpy as np
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    name = "energy_map" if world == 1 else f"energy_map_rank{rank}"
+    rows, width = out.shape
+    keep = max(1, DUMP_BUDGET_BYTES // world // (4 * width))
+    if keep >= rows:
+        arr = out.cpu().numpy()
+    else:
+        picked = np.sort(np.random.default_rng(20240 + rank).choice(rows, size=keep, replace=False))
+        # the band's first and last rows (frame border / halo-dependent rows) always
+        picked[0], picked[-1] = 0, rows - 1
+        arr = out.index_select(0, torch.from_numpy(picked).to(out.device)).cpu().numpy()
+        np.save(os.path.join(directory, name + "_rows.npy"), picked.astype(np.float64))
+    np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float32))
+
+
 def cpu_rehearsal(args):
     """The rank/band/halo plumbing of a step without a GPU: every rank holds
     its band of the global frame with the halo rows zeroed, exchanges halos
@@ -577,7 +631,7 @@ def main():
     torch.cuda.set_device(gpu)
     dev = torch.device("cuda", gpu)
     gloo = args.dist_backend == "gloo"
-    rccl_log = D.rccl_log_setup("dcte-bench") if world > 1 and not gloo else None
+    rccl_log = D.rccl_log_setup("dcte-bench") if args.full and world > 1 and not gloo else None
     if world > 1:
         if gloo:
             dist.init_process_group("gloo")
@@ -716,8 +770,11 @@ def main():
     valu_per_px = pmc.get("valu_lane_ops_per_px")
     valu_rate = (px_per_rank * valu_per_px / (kernel_ms_per_step * 1e-3)) if valu_per_px else None
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rank, world)
+
     check = None
-    if args.check or (world > 1 and not args.no_check):
+    if args.check or (args.full and world > 1 and not args.no_check):
         # regenerate this band's rows INCLUDING the halo rows straight from the
         # global frame definition and recompute without any exchange
         ref_in = synth.natural_rows(band.row0, band.rows, W, 3, seed=0, device=dev)
@@ -737,7 +794,7 @@ def main():
     # step, timed over `reps` exchanges on their own, max over ranks; and which
     # RCCL transport carried them (the ranks' RCCL INFO logs)
     exchange = None
-    if world > 1 and not gloo:
+    if args.full and world > 1 and not gloo:
         reps = 20
         for r in D.exchange_halos(buf, band):
             r.wait()
@@ -768,7 +825,7 @@ def main():
     # end to end: the step plus the gather of every band's
     # map to rank 0 over RCCL, reported beside the kernel-only metric
     e2e = None
-    if world > 1 and not gloo and not args.no_e2e:
+    if args.full and world > 1 and not gloo and not args.no_e2e:
         reps = 3
         D.gather_bands(out, band)                     # warm
         torch.cuda.synchronize()
@@ -797,6 +854,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": bool(args.full),
             "ms_per_step": round(ms_per_step, 4),
             # host time to ISSUE one step (max over ranks): near ms_per_step
             # means the launches, not the GPU, set the pace
@@ -860,22 +918,24 @@ def main():
                                              "halos over RCCL's socket transport on loopback)")
         if world > 1 and (gloo or args.shared_gpu) and ndev < world:
             res["config"]["parallelism"] += f"; {world} ranks share {ndev} GPU(s)"
-        if world == 1 and not args.no_stress:
+        # everything below runs after the timed region and only with --full
+        one_full = args.full and world == 1
+        if one_full and not args.no_stress:
             res["stress"] = stress(ctx, n, S, e, t, dev, stream)
-        if world == 1 and not args.no_exact:
+        if one_full and not args.no_exact:
             res["exact"] = exact(n, S, e, t, dev, buf)
-        if world == 1 and not args.no_configs and S == 16384 and n == 8:
+        if one_full and not args.no_configs and S == 16384 and n == 8:
             res["configs_1gpu"] = other_configs(ctx, e, t, dev, stream)
         # (r05 timed the host path before configs_1gpu: after other device
         # work its SDMA download and upload were serialised by the runtime, 38
         # instead of 22.4 ms; since r06 the download is a copy kernel, and
         # the order no longer matters -- tools/host_diag.py)
-        if world == 1 and not args.no_host_path:
+        if one_full and not args.no_host_path:
             res["host_path"] = host_path(ctx, buf, n, e, t)
             res["host_path_vertical"] = host_path_vertical(ctx, buf, n, e, t)
             if S > 4096:                       # BASELINE configs[1]'s frame size, a 4096^2 crop
                 res["host_path_4096"] = host_path(ctx, buf[:4096, :4096].contiguous(), n, e, t, iters=7)
-        if world == 1 and not args.no_cpu_baseline:
+        if one_full and not args.no_cpu_baseline:
             rows = args.cpu_rows or max(64, S // 2)
             rows = min(rows, H)
             host = buf[:min(H, rows + n)].cpu().numpy()

@@ -357,6 +357,13 @@ inline TF fmaxf(const TF& x, const TF& y)
     return r;
 }
 
+// the fp64 header spells them fabs / fmax (r64::col8; the bound itself only
+// tracks r64::transform, but the header has to compile over TF as a whole)
+using ::fabs;
+using ::fmax;
+inline TF fabs(const TF& x) { return fabsf(x); }
+inline TF fmax(const TF& x, const TF& y) { return fmaxf(x, y); }
+
 #define float TF
 #include "dcte_passes.h"
 #undef float

@@ -56,7 +56,7 @@ def test_bands_over_rccl(world, H, W, n):
 @pytest.mark.gpu
 def test_config4_bench_eight_ranks_on_one_gpu():
     """BASELINE configs[3] as the driver's scaling run executes it, rehearsed
-    on one GPU: bench.py --gpus 8 self-launches 8 RCCL ranks (one 16384^2 RGB
+    on one GPU: bench.py --full --gpus 8 self-launches 8 RCCL ranks (one 16384^2 RGB
     frame, 2048-row bands, halos over RCCL point-to-point; distinct
     NCCL_HOSTIDs so RCCL accepts 8 ranks on one device), times 3 steps, then
     re-maps every band from regenerated rows without any exchange and
@@ -64,7 +64,7 @@ def test_config4_bench_eight_ranks_on_one_gpu():
     rank 0 (end_to_end).  Basis: the band halo of src/render.c:146-152."""
     import signal
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--shared-gpu",
-           "--steps", "3", "--warmup", "1"]
+           "--steps", "3", "--warmup", "1", "--full"]
     p = subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                          start_new_session=True)
     try:
