@@ -1205,6 +1205,9 @@ int dcte_seam_carve_device(dcte_ctx* ctx, int device, const void* d_px, long lon
     DCTE_ARG(ctx, d_px && d_seam && d_map && d_px_out && d_map_out);
     DCTE_ARG(ctx, rowstride >= (long long)w * bpp && out_rowstride >= (long long)(w - 1) * bpp);
     DCTE_ARG(ctx, map_stride >= w && map_out_stride >= w - 1);
+    // in place is both or neither: the copying kernel on one aliased buffer corrupts its rows
+    DCTE_ARG(ctx, (d_px_out == d_px && out_rowstride == rowstride) ==
+                      (d_map_out == d_map && map_out_stride == map_stride));
     Device& d = ctx->devs[device];
     hipStream_t s = (hipStream_t)stream;
     DCTE_HIP(ctx, hipSetDevice(d.id));

@@ -25,11 +25,19 @@ namespace dcte {
 __device__ __forceinline__ unsigned fkey(float f) { return norm_fkey(f); }
 __device__ __forceinline__ float funkey(unsigned k) { return norm_funkey(k); }
 
-// keys[0] = min key, keys[1] = max key; caller initialises to (~0u, 0u)
+// keys[0] = min key, keys[1] = max key; caller initialises to (~0u, 0u).
+// e is float-aligned only (a row slice of an odd-width map): the <= 3 floats
+// below the first 16-byte boundary go to the first threads one by one, and
+// the float4 loop runs on the aligned rest.
 __global__ __launch_bounds__(256) void dcte_minmax(const float* __restrict__ e, long long n,
                                                    unsigned* keys)
 {
     unsigned kmin = 0xffffffffu, kmax = 0u;
+    const unsigned mis = (unsigned)((reinterpret_cast<uintptr_t>(e) >> 2) & 3u);
+    const long long head = min(n, (long long)((4u - mis) & 3u));
+    if (blockIdx.x == 0 && threadIdx.x < head) kmin = kmax = fkey(e[threadIdx.x]);
+    e += head;
+    n -= head;
     const long long stride = (long long)gridDim.x * blockDim.x * 4;
     for (long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += stride) {
         if (i + 3 < n) {

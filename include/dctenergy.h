@@ -234,7 +234,8 @@ int dcte_energy_map_device2(dcte_ctx *ctx, int device, const void *d_px,
  *   In place: d_px_out == d_px with the same row stride AND d_map_out ==
  *   d_map with the same stride -- only the part right of the seam moves (the
  *   frame keeps its row stride, one pixel narrower).  Otherwise the output
- *   buffers must not overlap the inputs.  Stream-ordered. */
+ *   buffers must not overlap the inputs; exactly one of the two in place
+ *   (frame or map, not both) is DCTE_EINVAL.  Stream-ordered. */
 int dcte_seam_carve_device(dcte_ctx *ctx, int device, const void *d_px, long long rowstride,
                            int w, int h, int bpp, const int *d_seam, const float *d_map,
                            long long map_stride, void *d_px_out, long long out_rowstride,

@@ -808,6 +808,79 @@ def test_energy_windows_bit_exact(ctx, n):
         assert np.array_equal(got, ref), n
 
 
+def _windows_device(ctx, win, e, t, guard=8):
+    """dcte_energy_windows_device on a K x N x N float64 batch -> (K energies,
+    the `guard` floats behind them as int32; they were set to 0x7fc0a5a5)."""
+    torch = _torch()
+    d_win = torch.from_numpy(win).cuda()
+    K, n = win.shape[:2]
+    out = torch.full((K + guard,), 0x7FC0A5A5, dtype=torch.int32, device="cuda")
+    rc = dctenergy.lib().dcte_energy_windows_device(ctx._h, 0, d_win.data_ptr(), K, n, e, t,
+                                                    out.data_ptr(),
+                                                    torch.cuda.current_stream().cuda_stream)
+    assert rc == dctenergy.DCTE_OK
+    torch.cuda.synchronize()
+    o = out.cpu().numpy()
+    return o[:K].view(np.float32), o[K:]
+
+
+@pytest.mark.parametrize("n", [2, 4, 8, 16])
+def test_energy_windows_past_one_stride(ctx, n):
+    """The grid of dcte_windows is capped at 2048 workgroups: one stride is
+    524 288 windows for N <= 8 (a lane each) and 32 768 for N = 16 (16 lanes
+    each, the `rounds` loop of the LDS path).  524288 + 300 windows (N = 16:
+    2 * 32768 + 5, a partial third round) drawn from 257 distinct ones --
+    random, luma-quantised, tie-prone -- with a stride coprime to 257, so a
+    window of a later pass answered with another pass's data shows: bit-equal
+    to the oracle, host and device entry, nothing written past `count`.
+    N = 16 also with 17 windows: a workgroup with one valid slot."""
+    rng = np.random.default_rng(140 + n)
+    pool = np.concatenate([rng.random((86, n, n)),
+                           O.luma_plane(rng.integers(0, 256, (86, n, n, 3), dtype=np.uint8)),
+                           (rng.random((85, n, n)) < 0.05) * (254 / 255) + 1 / 255])
+    assert len(pool) == 257
+    ref = np.array([O.window_energy(x, 0.3, 0.7) for x in pool], np.float32)
+    assert len(np.unique(ref)) > 100                       # a mixed-up window would show
+    for count in ((2 * 32768 + 5, 17) if n == 16 else (524288 + 300,)):
+        idx = (np.arange(count) * 7919) % 257
+        batch = pool[idx]
+        want = ref[idx]
+        got = ctx.energy_windows(batch, 0.3, 0.7)
+        assert np.array_equal(got, want), (n, count, "host", np.flatnonzero(got != want)[:5])
+        got, guard = _windows_device(ctx, batch, 0.3, 0.7)
+        assert np.array_equal(got, want), (n, count, "device", np.flatnonzero(got != want)[:5])
+        assert (guard == 0x7FC0A5A5).all(), (n, count)
+
+
+def _rgba_frames():
+    rnd = np.random.default_rng(45).integers(0, 256, (130, 67, 4), dtype=np.uint8)
+    rnd[:, ::5] //= 9                                      # ties: refinement on the transposed frame
+    return [load_input("rgba_45x38.npy"), rnd]
+
+
+@pytest.mark.parametrize("n", [2, 4, 8, 16])
+def test_rgba_transposed_paths(ctx, n):
+    """dcte_transpose_u8<4>: RGBA preview layers through the transposed host
+    map and dcte_energy_map2, on frames whose sides are no multiple of the
+    64-pixel transpose tile (one of them more than one tile tall)."""
+    for img in _rgba_frames():
+        tr = np.ascontiguousarray(np.swapaxes(img, 0, 1))
+        a = ctx.energy_map(img, n, 0.3, 0.7, semantics=dctenergy.DCTE_PREVIEW)
+        b = ctx.energy_map(img, n, 0.3, 0.7, semantics=dctenergy.DCTE_PREVIEW, transposed=True)
+        assert np.array_equal(b, ctx.energy_map(tr, n, 0.3, 0.7, semantics=dctenergy.DCTE_PREVIEW))
+        _assert_tol(b, O.preview_map(tr, n, 0.3, 0.7), f"rgba transposed {img.shape} n={n}")
+        o, ot = ctx.energy_map2(img, n, 0.3, 0.7, semantics=dctenergy.DCTE_PREVIEW)
+        assert np.array_equal(o, a) and np.array_equal(ot, b), (img.shape, n)
+
+
+def test_rgba_transposed_exact():
+    with dctenergy.Context(ngpus=1, exact=True) as ex:
+        for img in _rgba_frames():
+            tr = np.ascontiguousarray(np.swapaxes(img, 0, 1))
+            got = ex.energy_map(img, 8, 0.3, 0.7, semantics=dctenergy.DCTE_PREVIEW, transposed=True)
+            assert np.array_equal(got.view(np.uint32), O.preview_map(tr, 8, 0.3, 0.7).view(np.uint32))
+
+
 @pytest.mark.parametrize("n", [4, 8, 16])
 def test_grey_rgb_refinement_paths(n):
     """The dense refinement walks read liblqr RGB luma through one table when

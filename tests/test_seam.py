@@ -131,6 +131,59 @@ def test_carve_bad_arguments(ctx):
         assert rc == dctenergy.DCTE_EINVAL
 
 
+def test_carve_partly_in_place_is_refused(ctx):
+    """In place is both buffers or neither: the frame in place with a separate
+    map output (or the other way round) would run the copying kernel on
+    aliased rows.  Both mixed forms are DCTE_EINVAL and write nothing; the
+    fully in-place and the fully separate call still succeed and agree."""
+    torch = _torch()
+    img = load_input("natural_rgb_73x59.npy")
+    h, w = img.shape[:2]
+    st = torch.cuda.current_stream().cuda_stream
+    px = torch.from_numpy(img).cuda()
+    m = torch.empty((h, w), dtype=torch.float32, device="cuda")
+    ctx.energy_map_tensor(px, m, 8, 0.3, 0.7)
+    seam = torch.from_numpy(random_seams(h, w, seed=2, count=1)[0]).cuda()
+    px2, m2 = torch.zeros_like(px), torch.zeros_like(m)
+    px0, m0 = px.clone(), m.clone()
+    L = dctenergy.lib()
+
+    def call(po, mo):
+        return L.dcte_seam_carve_device(ctx._h, 0, px.data_ptr(), px.stride(0), w, h, 3,
+                                        seam.data_ptr(), m.data_ptr(), m.stride(0), po.data_ptr(),
+                                        po.stride(0), mo.data_ptr(), mo.stride(0), 8, 0.3, 0.7, 0, st)
+    assert call(px, m2) == dctenergy.DCTE_EINVAL          # frame in place, map copied
+    assert call(px2, m) == dctenergy.DCTE_EINVAL          # map in place, frame copied
+    torch.cuda.synchronize()
+    assert torch.equal(px, px0) and torch.equal(m, m0)
+    assert not px2.any() and not m2.any()
+    assert call(px2, m2) == dctenergy.DCTE_OK             # separate
+    assert call(px, m) == dctenergy.DCTE_OK               # in place
+    torch.cuda.synchronize()
+    assert torch.equal(px[:, :w - 1], px2[:, :w - 1]) and torch.equal(m[:, :w - 1], m2[:, :w - 1])
+    assert np.array_equal(px2[:, :w - 1].cpu().numpy(), carve(img, seam.cpu().numpy()))
+
+
+@pytest.mark.parametrize("sem", [0, 1])
+@pytest.mark.parametrize("n", [8, 16])
+def test_points_in_many_blocks(ctx, n, sem):
+    """Every pixel of a 300 x 200 RGB frame as a point (60 000 points, 235
+    workgroups of dcte_points): bit-equal to the map, host and device entry."""
+    torch = _torch()
+    rng = np.random.default_rng(60 + n)
+    img = rng.integers(0, 256, (200, 300, 3), dtype=np.uint8)
+    img[:, ::5] //= 9                                      # ties: the points' refinement runs
+    yy, xx = np.mgrid[0:200, 0:300]
+    xy = np.stack([xx.ravel(), yy.ravel()], 1).astype(np.int32)
+    full = ctx.energy_map(img, n, 0.15, 0.85, semantics=sem)
+    assert np.array_equal(ctx.energy_points(img, xy, n, 0.15, 0.85, semantics=sem), full.ravel())
+    out = torch.full((len(xy),), np.nan, dtype=torch.float32, device="cuda")
+    ctx.energy_points_tensor(torch.from_numpy(img).cuda(), torch.from_numpy(xy).cuda(), out, n,
+                             0.15, 0.85, semantics=sem)
+    torch.cuda.synchronize()
+    assert np.array_equal(out.cpu().numpy(), full.ravel())
+
+
 @pytest.mark.parametrize("n", [2, 4, 8, 16])
 @pytest.mark.parametrize("sem,name", [(0, "natural_rgb_73x59.npy"), (0, "wilber_rgb_74x59.npy"),
                                       (1, "rgba_45x38.npy"), (1, "natural_grey_200x120.npy")])

@@ -224,6 +224,24 @@ def test_host_carve_transposed(ctx):
     assert np.array_equal(cols, cols_t)
 
 
+def test_host_carve_transposed_rgba(ctx):
+    """The same for RGBA preview layers (dcte_transpose_u8<4> both ways), frame
+    sides no multiple of the 64-pixel transpose tile."""
+    rnd = np.random.default_rng(46).integers(0, 256, (130, 67, 4), dtype=np.uint8)
+    for img in (load_input("rgba_45x38.npy"), rnd):
+        h, w = img.shape[:2]
+        out, cols = ctx.carve(img, 5, 8, 0.3, 0.7, semantics=dctenergy.DCTE_PREVIEW, transposed=True)
+        tr = np.ascontiguousarray(np.swapaxes(img, 0, 1))
+        out_t, cols_t = ctx.carve(tr, 5, 8, 0.3, 0.7, semantics=dctenergy.DCTE_PREVIEW)
+        assert out.shape == (h - 5, w, 4)
+        assert np.array_equal(out, np.swapaxes(out_t, 0, 1))
+        assert np.array_equal(cols, cols_t)
+        host = tr                                          # and the pixels are the seams' carve
+        for s in cols_t:
+            host = carve(host, s)
+        assert np.array_equal(out_t, host)
+
+
 def test_host_carve_edges(ctx):
     img = load_input("natural_grey_200x120.npy")
     out, cols = ctx.carve(img, 0, 8)
