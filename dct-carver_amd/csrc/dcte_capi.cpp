@@ -1497,16 +1497,33 @@ int dcte_seam_find(dcte_ctx* ctx, const float* map, int w, int h, int* seam)
     return DCTE_OK;
 }
 
-int dcte_carve(dcte_ctx* ctx, const uint8_t* px, int w, int h, int bpp, size_t rowstride, int n,
+}  // extern "C"
+
+namespace {
+
+// Where carve_loop leaves its results (the first device's staging buffer)
+struct CarveLoop {
+    int W = 0, H = 0;              // the frame that was carved (transposed: h x w)
+    size_t pitch = 0;              // its row pitch, W * bpp
+    uint8_t* d_px = nullptr;       // carved frame, (W - seams) x H at that pitch
+    float* d_map = nullptr;        // its energies (row stride W)
+    int* d_seams = nullptr;        // seams x H step columns
+    uint8_t* d_tmp = nullptr;      // transposed: a second frame-sized buffer
+};
+
+// The loop liblqr runs in lqr_carver_resize, shared by dcte_carve and
+// dcte_resizer_create: upload (and transpose), energy map, then (seam ->
+// carve in place + energy update) per step, all in HBM on the first device.
+// d_orig (optional): receives the W x H frame (pitch W * bpp) before the first
+// step.  hs: seams * H host ints, the step columns; on return the stream is
+// idle and no search has timed out (a seam starting with -1 re-runs the whole
+// loop band-wise via dp_fall_back, or is DCTE_EHIP).  Arguments are checked by
+// the callers.
+int carve_loop(dcte_ctx* ctx, const uint8_t* px, int w, int h, int bpp, size_t rowstride, int n,
                float edges, float textures, int semantics, int seams, int transposed,
-               uint8_t* out, int* seam_cols)
+               uint8_t* d_orig, int* hs, CarveLoop* L)
 {
-    DeviceGuard guard_;
-    if (!ctx) return DCTE_EINVAL;
-    DCTE_ARG(ctx, px && out && valid_n(n) && valid_sem_bpp(semantics, bpp) && w > 0 && h > 0);
-    DCTE_ARG(ctx, rowstride >= (size_t)w * bpp);
     const int W = transposed ? h : w, H = transposed ? w : h;   // the frame that is carved
-    DCTE_ARG(ctx, seams >= 0 && seams < W);
     ctx->last_refined = 0;
     Device& d = ctx->devs[0];
     int rc = ensure_stream(ctx, d);
@@ -1539,6 +1556,8 @@ int dcte_carve(dcte_ctx* ctx, const uint8_t* px, int w, int h, int bpp, size_t r
         DCTE_HIP(ctx, hipMemcpy2DAsync(d_px, pitch, px, rowstride, pitch, h,
                                        hipMemcpyHostToDevice, s));
     }
+    if (d_orig)   // the loop carves in place
+        DCTE_HIP(ctx, hipMemcpyAsync(d_orig, d_px, pitch * (size_t)H, hipMemcpyDeviceToDevice, s));
     // map, then (seam -> carve in place + energy update) per step, all in HBM
     rc = run_device(ctx, d, d_px, (long long)pitch, W, H, bpp, 0, H, 0, H, n, edges, textures,
                     semantics, d_map, W, s);
@@ -1555,13 +1574,7 @@ int dcte_carve(dcte_ctx* ctx, const uint8_t* px, int w, int h, int bpp, size_t r
         return rc;
     }
     // the seams first: a search that timed out is re-run from the caller's px
-    // before anything is written to out (which may overlap px)
-    std::vector<int> own;
-    int* hs = seam_cols;
-    if (seams > 0 && !hs) {
-        own.resize((size_t)seams * H);
-        hs = own.data();
-    }
+    // before anything is written to the caller's output (which may overlap px)
     if (seams > 0) {
         DCTE_HIP(ctx, hipMemcpyAsync(hs, d_seams, sizeof(int) * (size_t)seams * H,
                                      hipMemcpyDeviceToHost, s));
@@ -1569,20 +1582,56 @@ int dcte_carve(dcte_ctx* ctx, const uint8_t* px, int w, int h, int bpp, size_t r
     }
     for (int k = 0; k < seams; k++)
         if (hs[(size_t)k * H] < 0) {
-            if (dp_fall_back(d, s))   // out is untouched: carve again band-wise
-                return dcte_carve(ctx, px, w, h, bpp, rowstride, n, edges, textures, semantics,
-                                  seams, transposed, out, seam_cols);
+            if (dp_fall_back(d, s))   // nothing handed out yet: carve again band-wise
+                return carve_loop(ctx, px, w, h, bpp, rowstride, n, edges, textures, semantics,
+                                  seams, transposed, d_orig, hs, L);
             ctx->last_error = "seam search timed out waiting for a neighbour tile";
             return DCTE_EHIP;
         }
+    L->W = W;
+    L->H = H;
+    L->pitch = pitch;
+    L->d_px = d_px;
+    L->d_map = d_map;
+    L->d_seams = d_seams;
+    L->d_tmp = d_tmp;
+    return DCTE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dcte_carve(dcte_ctx* ctx, const uint8_t* px, int w, int h, int bpp, size_t rowstride, int n,
+               float edges, float textures, int semantics, int seams, int transposed,
+               uint8_t* out, int* seam_cols)
+{
+    DeviceGuard guard_;
+    if (!ctx) return DCTE_EINVAL;
+    DCTE_ARG(ctx, px && out && valid_n(n) && valid_sem_bpp(semantics, bpp) && w > 0 && h > 0);
+    DCTE_ARG(ctx, rowstride >= (size_t)w * bpp);
+    const int W = transposed ? h : w, H = transposed ? w : h;   // the frame that is carved
+    DCTE_ARG(ctx, seams >= 0 && seams < W);
+    std::vector<int> own;
+    int* hs = seam_cols;
+    if (seams > 0 && !hs) {
+        own.resize((size_t)seams * H);
+        hs = own.data();
+    }
+    CarveLoop L;
+    int rc = carve_loop(ctx, px, w, h, bpp, rowstride, n, edges, textures, semantics, seams,
+                        transposed, nullptr, hs, &L);
+    if (rc) return rc;
+    hipStream_t s = ctx->devs[0].stream;
+    const size_t pitch = L.pitch;
     const int Wo = W - seams;
     if (transposed) {   // H x Wo carved frame -> Wo x H = (h - seams) x w
-        DCTE_HIP(ctx, dcte::launch_transpose_u8(d_px, (long long)pitch, H, Wo, bpp, d_tmp,
+        DCTE_HIP(ctx, dcte::launch_transpose_u8(L.d_px, (long long)pitch, H, Wo, bpp, L.d_tmp,
                                                 (long long)H * bpp, s));
-        DCTE_HIP(ctx, hipMemcpyAsync(out, d_tmp, (size_t)Wo * (size_t)H * bpp,
+        DCTE_HIP(ctx, hipMemcpyAsync(out, L.d_tmp, (size_t)Wo * (size_t)H * bpp,
                                      hipMemcpyDeviceToHost, s));
     } else {
-        DCTE_HIP(ctx, hipMemcpy2DAsync(out, (size_t)Wo * bpp, d_px, pitch, (size_t)Wo * bpp, H,
+        DCTE_HIP(ctx, hipMemcpy2DAsync(out, (size_t)Wo * bpp, L.d_px, pitch, (size_t)Wo * bpp, H,
                                        hipMemcpyDeviceToHost, s));
     }
     return sync_bands(ctx, 1);
@@ -1796,6 +1845,307 @@ void dcte_carver_destroy(dcte_carver* c)
 {
     DeviceGuard guard_;
     carver_free(c);
+}
+
+// ---- seam visibility map: device pieces ----
+int dcte_vmap_device(dcte_ctx* ctx, int device, const int* d_seams, int depth, int W, int H,
+                     int32_t* d_vmap, long long vmap_stride, void* stream)
+{
+    if (!ctx) return DCTE_EINVAL;
+    DeviceGuard guard_;
+    DCTE_ARG(ctx, device >= 0 && device < (int)ctx->devs.size());
+    DCTE_ARG(ctx, d_vmap && W >= 1 && H >= 1 && vmap_stride >= W);
+    DCTE_ARG(ctx, depth >= 0 && depth < W && (d_seams || depth == 0));
+    if (W > dcte::kVmapMaxW) return DCTE_ERANGE;
+    DCTE_HIP(ctx, hipSetDevice(ctx->devs[device].id));
+    dcte::VmapParams p{};
+    p.seams = d_seams;
+    p.depth = depth;
+    p.w = W;
+    p.h = H;
+    p.vmap = d_vmap;
+    p.stride = vmap_stride;
+    DCTE_HIP(ctx, dcte::launch_vmap(p, (hipStream_t)stream));
+    return DCTE_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+bool valid_bpp(int bpp) { return bpp == 1 || bpp == 3 || bpp == 4; }
+
+// bytes [a, a + (rows-1)*stride + row) and the same of b share a byte
+bool spans_overlap(const void* a, long long a_stride, long long a_row, const void* b,
+                   long long b_stride, long long b_row, int rows)
+{
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    const uintptr_t a1 = a0 + (uintptr_t)((long long)(rows - 1) * a_stride + a_row);
+    const uintptr_t b1 = b0 + (uintptr_t)((long long)(rows - 1) * b_stride + b_row);
+    return a0 < b1 && b0 < a1;
+}
+
+dcte::RenderParams render_params(const void* d_px, long long rowstride, int w, int h, int bpp,
+                                 const int32_t* d_vmap, long long vmap_stride, int depth, int delta,
+                                 void* d_out, long long out_rowstride)
+{
+    dcte::RenderParams p{};
+    p.px = static_cast<const uint8_t*>(d_px);
+    p.rowstride = rowstride;
+    p.w = w;
+    p.h = h;
+    p.bpp = bpp;
+    p.vmap = d_vmap;
+    p.vmap_stride = vmap_stride;
+    p.depth = depth;
+    p.delta = delta;
+    p.out = static_cast<uint8_t*>(d_out);
+    p.out_rowstride = out_rowstride;
+    return p;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dcte_vmap_render_device(dcte_ctx* ctx, int device, const void* d_px, long long rowstride, int W,
+                            int H, int bpp, const int32_t* d_vmap, long long vmap_stride, int depth,
+                            int delta, void* d_out, long long out_rowstride, void* stream)
+{
+    if (!ctx) return DCTE_EINVAL;
+    DeviceGuard guard_;
+    DCTE_ARG(ctx, device >= 0 && device < (int)ctx->devs.size());
+    DCTE_ARG(ctx, d_px && d_vmap && d_out && valid_bpp(bpp) && W >= 1 && H >= 1);
+    DCTE_ARG(ctx, depth >= 0 && depth < W && delta >= -depth && delta <= depth);
+    DCTE_ARG(ctx, rowstride >= (long long)W * bpp && vmap_stride >= W &&
+                      out_rowstride >= (long long)(W + delta) * bpp);
+    DCTE_ARG(ctx, !spans_overlap(d_px, rowstride, (long long)W * bpp, d_out, out_rowstride,
+                                 (long long)(W + delta) * bpp, H));
+    DCTE_ARG(ctx, !spans_overlap(d_vmap, vmap_stride * 4, (long long)W * 4, d_out, out_rowstride,
+                                 (long long)(W + delta) * bpp, H));
+    if (W > dcte::kVmapMaxW) return DCTE_ERANGE;
+    DCTE_HIP(ctx, hipSetDevice(ctx->devs[device].id));
+    DCTE_HIP(ctx, dcte::launch_vmap_render(render_params(d_px, rowstride, W, H, bpp, d_vmap,
+                                                         vmap_stride, depth, delta, d_out,
+                                                         out_rowstride),
+                                           (hipStream_t)stream));
+    return DCTE_OK;
+}
+
+int dcte_vmap_seams_u8_device(dcte_ctx* ctx, int device, const void* d_px, long long rowstride, int w,
+                              int h, int bpp, const int32_t* d_vmap, long long vmap_stride, int depth,
+                              void* d_out, long long out_rowstride, void* stream)
+{
+    if (!ctx) return DCTE_EINVAL;
+    DeviceGuard guard_;
+    DCTE_ARG(ctx, device >= 0 && device < (int)ctx->devs.size());
+    DCTE_ARG(ctx, d_px && d_vmap && d_out && valid_bpp(bpp) && w >= 1 && h >= 1 && depth >= 0);
+    DCTE_ARG(ctx, rowstride >= (long long)w * bpp && vmap_stride >= w &&
+                      out_rowstride >= (long long)w * bpp);
+    DCTE_ARG(ctx, !spans_overlap(d_px, rowstride, (long long)w * bpp, d_out, out_rowstride,
+                                 (long long)w * bpp, h));
+    if (w > dcte::kVmapMaxW) return DCTE_ERANGE;
+    DCTE_HIP(ctx, hipSetDevice(ctx->devs[device].id));
+    DCTE_HIP(ctx, dcte::launch_vmap_seams_u8(render_params(d_px, rowstride, w, h, bpp, d_vmap,
+                                                           vmap_stride, depth, 0, d_out,
+                                                           out_rowstride),
+                                             (hipStream_t)stream));
+    return DCTE_OK;
+}
+
+}  // extern "C"
+
+// ---- resizer: the original frame and its visibility map in HBM ----
+struct dcte_resizer {
+    dcte_ctx* ctx = nullptr;
+    int w = 0, h = 0;          // the caller's frame
+    int W = 0, H = 0;          // the carved frame (transposed: h x w)
+    int bpp = 0, depth = 0;
+    bool transposed = false;
+    size_t pitch = 0;          // W * bpp
+    uint8_t* d_px = nullptr;   // the original carved-orientation frame, W x H
+    int32_t* d_vmap = nullptr; // its visibility map, W x H (row stride W)
+};
+
+namespace {
+
+void resizer_free(dcte_resizer* r)
+{
+    if (!r) return;
+    if (!r->ctx->devs.empty() && hipSetDevice(r->ctx->devs[0].id) == hipSuccess) {
+        if (r->ctx->devs[0].stream) (void)hipStreamSynchronize(r->ctx->devs[0].stream);
+        if (r->d_px) (void)hipFree(r->d_px);
+        if (r->d_vmap) (void)hipFree(r->d_vmap);
+    }
+    delete r;
+}
+
+// the end of a resizer call: wait for the stream; on failure nothing of the
+// call is left in flight
+int resizer_sync(dcte_ctx* ctx, hipStream_t s)
+{
+    hipError_t e = hipStreamSynchronize(s);
+    if (e == hipSuccess) return DCTE_OK;
+    const int rc = hip_fail(ctx, e, "hipStreamSynchronize");
+    drain(ctx, 1);
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dcte_resizer_create(dcte_ctx* ctx, const uint8_t* px, int w, int h, int bpp, size_t rowstride,
+                        int n, float edges, float textures, int semantics, int depth,
+                        int transposed, int* seam_cols, dcte_resizer** out)
+{
+    if (!ctx || !out) return DCTE_EINVAL;
+    DeviceGuard guard_;
+    *out = nullptr;
+    DCTE_ARG(ctx, px && valid_n(n) && valid_sem_bpp(semantics, bpp) && w > 0 && h > 0);
+    DCTE_ARG(ctx, rowstride >= (size_t)w * bpp);
+    const int W = transposed ? h : w, H = transposed ? w : h;   // the frame that is carved
+    DCTE_ARG(ctx, depth >= 0 && depth < W);
+    if ((unsigned long long)W * (unsigned long long)H >= (1ULL << 32)) return DCTE_ERANGE;
+    Device& d = ctx->devs[0];
+    int rc = ensure_stream(ctx, d);
+    if (rc) return rc;
+    dcte_resizer* r = new (std::nothrow) dcte_resizer;
+    if (!r) return DCTE_ENOMEM;
+    r->ctx = ctx;
+    r->w = w;
+    r->h = h;
+    r->W = W;
+    r->H = H;
+    r->bpp = bpp;
+    r->depth = depth;
+    r->transposed = transposed != 0;
+    r->pitch = (size_t)W * bpp;
+    std::vector<int> own;
+    int* hs = seam_cols;
+    hipError_t e;
+    if ((e = hipMalloc(&r->d_px, r->pitch * (size_t)H)) != hipSuccess ||
+        (e = hipMalloc(&r->d_vmap, sizeof(int32_t) * (size_t)W * (size_t)H)) != hipSuccess) {
+        rc = hip_fail(ctx, e, "hipMalloc resizer");
+        resizer_free(r);
+        return rc;
+    }
+    if (depth > 0 && !hs) {
+        own.resize((size_t)depth * H);
+        hs = own.data();
+    }
+    CarveLoop L;
+    rc = carve_loop(ctx, px, w, h, bpp, rowstride, n, edges, textures, semantics, depth, transposed,
+                    r->d_px, hs, &L);
+    if (rc == DCTE_OK)
+        rc = dcte_vmap_device(ctx, 0, L.d_seams, depth, W, H, r->d_vmap, W, d.stream);
+    if (rc == DCTE_OK) rc = sync_bands(ctx, 1);
+    else drain(ctx, 1);
+    if (rc) {
+        resizer_free(r);
+        return rc;
+    }
+    *out = r;
+    return DCTE_OK;
+}
+
+int dcte_resizer_depth(const dcte_resizer* r) { return r ? r->depth : 0; }
+
+int dcte_resizer_render(dcte_resizer* r, int delta, uint8_t* out)
+{
+    if (!r) return DCTE_EINVAL;
+    DeviceGuard guard_;
+    dcte_ctx* ctx = r->ctx;
+    DCTE_ARG(ctx, out && delta >= -r->depth && delta <= r->depth);
+    Device& d = ctx->devs[0];
+    int rc = ensure_stream(ctx, d);
+    if (rc) return rc;
+    hipStream_t s = d.stream;
+    const int Wo = r->W + delta;
+    const size_t opitch = (size_t)Wo * r->bpp, obytes = opitch * (size_t)r->H;
+    rc = ensure_buf(ctx, (void**)&d.d_u8, &d.u8_cap, obytes);
+    if (rc == DCTE_OK && r->transposed) rc = ensure_buf(ctx, (void**)&d.d_tr, &d.tr_cap, obytes);
+    if (rc) return rc;
+    rc = dcte_vmap_render_device(ctx, 0, r->d_px, (long long)r->pitch, r->W, r->H, r->bpp, r->d_vmap,
+                                 r->W, r->depth, delta, d.d_u8, (long long)opitch, s);
+    if (rc) return rc;
+    const uint8_t* res = d.d_u8;
+    if (r->transposed) {   // H x Wo rendered frame -> Wo x H = (h + delta) x w
+        DCTE_HIP(ctx, dcte::launch_transpose_u8(d.d_u8, (long long)opitch, r->H, Wo, r->bpp, d.d_tr,
+                                                (long long)r->H * r->bpp, s));
+        res = d.d_tr;
+    }
+    DCTE_HIP(ctx, hipMemcpyAsync(out, res, obytes, hipMemcpyDeviceToHost, s));
+    return resizer_sync(ctx, s);
+}
+
+int dcte_resizer_vmap(dcte_resizer* r, int32_t* vmap)
+{
+    if (!r) return DCTE_EINVAL;
+    DeviceGuard guard_;
+    dcte_ctx* ctx = r->ctx;
+    DCTE_ARG(ctx, vmap);
+    Device& d = ctx->devs[0];
+    int rc = ensure_stream(ctx, d);
+    if (rc) return rc;
+    hipStream_t s = d.stream;
+    const size_t vbytes = sizeof(int32_t) * (size_t)r->W * (size_t)r->H;
+    const void* res = r->d_vmap;
+    if (r->transposed) {   // an int32 entry moves as a 4-byte pixel
+        rc = ensure_buf(ctx, (void**)&d.d_tr, &d.tr_cap, vbytes);
+        if (rc) return rc;
+        DCTE_HIP(ctx, dcte::launch_transpose_u8(reinterpret_cast<const uint8_t*>(r->d_vmap),
+                                                (long long)r->W * 4, r->H, r->W, 4, d.d_tr,
+                                                (long long)r->H * 4, s));
+        res = d.d_tr;
+    }
+    DCTE_HIP(ctx, hipMemcpyAsync(vmap, res, vbytes, hipMemcpyDeviceToHost, s));
+    return resizer_sync(ctx, s);
+}
+
+int dcte_resizer_seams_u8(dcte_resizer* r, uint8_t* out)
+{
+    if (!r) return DCTE_EINVAL;
+    DeviceGuard guard_;
+    dcte_ctx* ctx = r->ctx;
+    DCTE_ARG(ctx, out);
+    Device& d = ctx->devs[0];
+    int rc = ensure_stream(ctx, d);
+    if (rc) return rc;
+    hipStream_t s = d.stream;
+    const size_t fbytes = r->pitch * (size_t)r->H;               // = w * h * bpp
+    const size_t vbytes = sizeof(int32_t) * (size_t)r->W * (size_t)r->H;
+    rc = ensure_buf(ctx, (void**)&d.d_u8, &d.u8_cap, fbytes);
+    if (rc) return rc;
+    const uint8_t* fr = r->d_px;                                 // the caller's orientation
+    const int32_t* vm = r->d_vmap;
+    if (r->transposed) {   // carved frame | its map, both transposed back: h = W rows of w = H
+        const size_t voff = (fbytes + 255) & ~(size_t)255;
+        rc = ensure_buf(ctx, (void**)&d.d_tr, &d.tr_cap, voff + vbytes);
+        if (rc) return rc;
+        DCTE_HIP(ctx, dcte::launch_transpose_u8(r->d_px, (long long)r->pitch, r->H, r->W, r->bpp,
+                                                d.d_tr, (long long)r->H * r->bpp, s));
+        DCTE_HIP(ctx, dcte::launch_transpose_u8(reinterpret_cast<const uint8_t*>(r->d_vmap),
+                                                (long long)r->W * 4, r->H, r->W, 4, d.d_tr + voff,
+                                                (long long)r->H * 4, s));
+        fr = d.d_tr;
+        vm = reinterpret_cast<const int32_t*>(d.d_tr + voff);
+    }
+    rc = dcte_vmap_seams_u8_device(ctx, 0, fr, (long long)r->w * r->bpp, r->w, r->h, r->bpp, vm, r->w,
+                                   r->depth, d.d_u8, (long long)r->w * r->bpp, s);
+    if (rc) {
+        drain(ctx, 1);
+        return rc;
+    }
+    DCTE_HIP(ctx, hipMemcpyAsync(out, d.d_u8, fbytes, hipMemcpyDeviceToHost, s));
+    return resizer_sync(ctx, s);
+}
+
+void dcte_resizer_destroy(dcte_resizer* r)
+{
+    if (!r) return;
+    DeviceGuard guard_;
+    resizer_free(r);
 }
 
 int dcte_energy_map(dcte_ctx* ctx, const uint8_t* px, int w, int h, int bpp, size_t rowstride,

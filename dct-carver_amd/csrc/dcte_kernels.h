@@ -177,6 +177,34 @@ struct DpParams {
                              // time when not every tile can be resident)
 };
 
+// Seam visibility map of a carve loop (dcte_vmap.hip): per-step columns ->
+// vmap[y][x] = k + 1 where step k removed original pixel (x, y), 0 where the
+// pixel survives.
+struct VmapParams {
+    const int* seams;        // depth x h: entry k * h + y = column step k removed from row y,
+                             // in that step's (w - k)-wide frame (clamped to it)
+    int depth, w, h;         // 0 <= depth < w
+    int32_t* vmap;           // w x h
+    long long stride;        // ints
+    int blk;                 // dcte_vmap_wide: pixels per counted block (set by the launcher)
+};
+
+// widest row the map kernels index with ints (a pass may look 1024 past the end)
+constexpr int kVmapMaxW = 0x7fffffff - 1024;
+
+// Render from / paint with a visibility map (dcte_vmap.hip)
+struct RenderParams {
+    const uint8_t* px;       // w x h frame
+    long long rowstride;
+    int w, h, bpp;
+    const int32_t* vmap;     // w x h
+    long long vmap_stride;   // ints
+    int depth;               // steps the map holds
+    int delta;               // render: output width w + delta, |delta| <= depth
+    uint8_t* out;            // render: (w + delta) x h; seams layer: w x h
+    long long out_rowstride;
+};
+
 // host-side launchers (dcte_kernels.hip)
 // ev_a / ev_b (or null): events the launch records at the kernel's start / end
 hipError_t launch_map(int n, int bpp, int sem, const MapParams& p, hipStream_t s, hipEvent_t ev_a = nullptr,
@@ -188,6 +216,10 @@ hipError_t launch_points(const SeamParams& p, hipStream_t s);
 hipError_t launch_band_gather(const BandParams& p, hipStream_t s);
 hipError_t launch_windows(const WinParams& p, hipStream_t s);
 hipError_t launch_seam_find(const DpParams& p, hipStream_t s, bool resident);
+hipError_t launch_vmap(const VmapParams& p, hipStream_t s);
+hipError_t launch_vmap_render(const RenderParams& p, hipStream_t s);
+hipError_t launch_vmap_seams_u8(const RenderParams& p, hipStream_t s);
+int vmap_wave_max_w(int words_per_lane);   // widest row of the one-wave map kernel (1 or 4 words)
 int dp_tile_cols();
 int dp_band_rows();
 int dp_super_bands();

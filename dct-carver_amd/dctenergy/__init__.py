@@ -55,7 +55,10 @@ EXPORTS = ("dcte_abi_version", "dcte_device_count", "dcte_create", "dcte_destroy
            "dcte_energy_window", "dcte_normalize_u8_host", "dcte_carver_create",
            "dcte_carver_step", "dcte_carver_width", "dcte_carver_height",
            "dcte_carver_band_width", "dcte_carver_destroy", "dcte_energy_map2",
-           "dcte_carver_create2")
+           "dcte_carver_create2", "dcte_vmap_device", "dcte_vmap_render_device",
+           "dcte_vmap_seams_u8_device", "dcte_resizer_create", "dcte_resizer_render",
+           "dcte_resizer_vmap", "dcte_resizer_seams_u8", "dcte_resizer_depth",
+           "dcte_resizer_destroy")
 
 _lib = None
 
@@ -180,6 +183,25 @@ def lib():
         getattr(L, fn).argtypes = [vp]
     L.dcte_carver_destroy.restype = None
     L.dcte_carver_destroy.argtypes = [vp]
+    L.dcte_vmap_device.restype = i
+    L.dcte_vmap_device.argtypes = [vp, i, vp, i, i, i, vp, ll, vp]
+    L.dcte_vmap_render_device.restype = i
+    L.dcte_vmap_render_device.argtypes = [vp, i, vp, ll, i, i, i, vp, ll, i, i, vp, ll, vp]
+    L.dcte_vmap_seams_u8_device.restype = i
+    L.dcte_vmap_seams_u8_device.argtypes = [vp, i, vp, ll, i, i, i, vp, ll, i, vp, ll, vp]
+    L.dcte_resizer_create.restype = i
+    L.dcte_resizer_create.argtypes = [vp, vp, i, i, i, ctypes.c_size_t, i, f, f, i, i, i, vp,
+                                      ctypes.POINTER(vp)]
+    L.dcte_resizer_render.restype = i
+    L.dcte_resizer_render.argtypes = [vp, i, vp]
+    L.dcte_resizer_vmap.restype = i
+    L.dcte_resizer_vmap.argtypes = [vp, vp]
+    L.dcte_resizer_seams_u8.restype = i
+    L.dcte_resizer_seams_u8.argtypes = [vp, vp]
+    L.dcte_resizer_depth.restype = i
+    L.dcte_resizer_depth.argtypes = [vp]
+    L.dcte_resizer_destroy.restype = None
+    L.dcte_resizer_destroy.argtypes = [vp]
     L.dcte_strerror.restype = ctypes.c_char_p
     L.dcte_strerror.argtypes = [ctypes.c_int]
     L.dcte_last_error.restype = ctypes.c_char_p
@@ -534,6 +556,102 @@ class Context:
                                      out.ctypes.data, cols.ctypes.data if seams else None))
         return out, cols
 
+    # -- seam visibility map: resize to any width, enlarge, "Seams" layer
+    def resizer(self, px, depth, n=8, edges=0.5, textures=0.5, semantics=DCTE_LQR,
+                transposed=False):
+        """Carve `depth` seams once (the loop of carve()) and keep the frame and
+        its visibility map in HBM -> Resizer: .render(delta) for any |delta| <=
+        depth, .vmap(), .seams_image(); .cols = the step columns carve() returns."""
+        px, h, w, bpp, rowstride = self._frame(px)
+        W, H = (h, w) if transposed else (w, h)
+        if not 0 <= depth < W:
+            raise DcteError(DCTE_EINVAL, f"depth must lie in [0, {W})")
+        cols = np.empty((depth, H), np.int32)
+        r = ctypes.c_void_p()
+        self._check(lib().dcte_resizer_create(self._h, px.ctypes.data, w, h, bpp, rowstride, n,
+                                              edges, textures, semantics, depth,
+                                              int(bool(transposed)),
+                                              cols.ctypes.data if depth else None,
+                                              ctypes.byref(r)))
+        return Resizer(self, r, (h, w) + px.shape[2:], bool(transposed), cols)
+
+    def resize(self, px, delta, n=8, edges=0.5, textures=0.5, semantics=DCTE_LQR,
+               transposed=False):
+        """The frame `delta` pixels wider (delta > 0: seams inserted) or narrower
+        (delta < 0: carve(px, -delta)[0]); rows instead of columns with
+        transposed=True.  One resizer of depth |delta|, one render."""
+        r = self.resizer(px, abs(delta), n, edges, textures, semantics, transposed)
+        try:
+            return r.render(delta)
+        finally:
+            r.close()
+
+    @staticmethod
+    def _stream(t, stream):
+        import torch
+        return torch.cuda.current_stream(t.device).cuda_stream if stream is None else stream
+
+    def vmap_tensor(self, seams, vmap, stream=None, device=0):
+        """Device version: seams int32 [depth, H] (contiguous), vmap int32 [H, W]
+        (row stride vmap.stride(0)); every entry of vmap is written."""
+        import torch
+        if seams.dtype != torch.int32 or vmap.dtype != torch.int32:
+            raise TypeError("seams and vmap must be int32")
+        if seams.dim() != 2 or not seams.is_contiguous() or vmap.dim() != 2 or vmap.stride(1) != 1:
+            raise ValueError("seams contiguous [depth, H]; vmap rows dense")
+        h, w = vmap.shape
+        depth = seams.shape[0]
+        if depth and seams.shape[1] != h:
+            raise ValueError("seams needs H entries per step")
+        self._check(lib().dcte_vmap_device(
+            self._h, device, ctypes.c_void_p(seams.data_ptr() if depth else None), depth, w, h,
+            ctypes.c_void_p(vmap.data_ptr()), vmap.stride(0),
+            ctypes.c_void_p(self._stream(vmap, stream))))
+        return vmap
+
+    @staticmethod
+    def _frame_tensor(px, what):
+        import torch
+        if px.dtype != torch.uint8 or px.dim() not in (2, 3):
+            raise TypeError(f"{what} must be an HxW or HxWxC uint8 tensor")
+        bpp = 1 if px.dim() == 2 else px.shape[2]
+        if px.stride(-1) != 1 or (px.dim() == 3 and px.stride(1) != bpp):
+            raise ValueError(f"{what}: pixels must be dense within a row")
+        return px.shape[0], px.shape[1], bpp
+
+    def vmap_render_tensor(self, px, vmap, depth, delta, out, stream=None, device=0):
+        """Device version: px uint8 [H, W(, C)], vmap int32 [H, W] -> out uint8
+        [H, W + delta(, C)]; row strides are the tensors' own."""
+        import torch
+        h, w, bpp = self._frame_tensor(px, "px")
+        ho, wo, bo = self._frame_tensor(out, "out")
+        if vmap.dtype != torch.int32 or vmap.dim() != 2 or vmap.stride(1) != 1:
+            raise TypeError("vmap must be int32 [H, W] with dense rows")
+        if (ho, wo, bo) != (h, w + delta, bpp) or tuple(vmap.shape) != (h, w):
+            raise ValueError("out must be H x (W + delta), vmap H x W")
+        self._check(lib().dcte_vmap_render_device(
+            self._h, device, ctypes.c_void_p(px.data_ptr()), px.stride(0), w, h, bpp,
+            ctypes.c_void_p(vmap.data_ptr()), vmap.stride(0), depth, delta,
+            ctypes.c_void_p(out.data_ptr()), out.stride(0),
+            ctypes.c_void_p(self._stream(px, stream))))
+        return out
+
+    def vmap_seams_tensor(self, px, vmap, depth, out, stream=None, device=0):
+        """Device version of the seams image: px, out uint8 [H, W(, C)], vmap
+        int32 [H, W], all in the caller's orientation."""
+        import torch
+        h, w, bpp = self._frame_tensor(px, "px")
+        if self._frame_tensor(out, "out") != (h, w, bpp):
+            raise ValueError("out must have px's shape")
+        if vmap.dtype != torch.int32 or tuple(vmap.shape) != (h, w) or vmap.stride(1) != 1:
+            raise TypeError("vmap must be int32 [H, W] with dense rows")
+        self._check(lib().dcte_vmap_seams_u8_device(
+            self._h, device, ctypes.c_void_p(px.data_ptr()), px.stride(0), w, h, bpp,
+            ctypes.c_void_p(vmap.data_ptr()), vmap.stride(0), depth,
+            ctypes.c_void_p(out.data_ptr()), out.stride(0),
+            ctypes.c_void_p(self._stream(px, stream))))
+        return out
+
     def seam_find_tensor(self, emap, seam, stream=None, device=0):
         """Device version: emap float32 [H, >=W] (row stride emap.stride(0)), seam int32 [H]."""
         import torch
@@ -591,7 +709,61 @@ class Carver:
             pass
 
 
-__all__ = ["Context", "Carver", "DcteError", "lib", "device_count", "LIB_PATH", "EXPORTS",
+class Resizer:
+    """dcte_resizer: the original frame and its seam visibility map in HBM --
+    the dialog's carve-once, render-many pattern (src/interface.c:131-135,
+    648-670).  cols: the step columns, as carve() returns them."""
+
+    def __init__(self, ctx, handle, shape, transposed, cols):
+        self._ctx, self._h, self._shape, self._transposed = ctx, handle, shape, transposed
+        self.cols = cols
+
+    @property
+    def depth(self):
+        return lib().dcte_resizer_depth(self._h)
+
+    def render(self, delta):
+        """The frame resized by delta, |delta| <= depth: h x (w + delta), or
+        (h + delta) x w for a transposed resizer."""
+        h, w = self._shape[:2]
+        hd, wd = (max(h + delta, 0), w) if self._transposed else (h, max(w + delta, 0))
+        shape = (hd, wd) + self._shape[2:]   # (a delta out of range: the library refuses)
+        out = np.empty(shape, np.uint8)
+        self._ctx._check(lib().dcte_resizer_render(self._h, delta, out.ctypes.data))
+        return out
+
+    def vmap(self):
+        """int32 h x w: k + 1 where step k removed the pixel, 0 where it survives."""
+        out = np.empty(self._shape[:2], np.int32)
+        self._ctx._check(lib().dcte_resizer_vmap(self._h, out.ctypes.data))
+        return out
+
+    def seams_image(self):
+        """The "Seams" layer (src/render.c:204-240): the frame with every removed
+        pixel painted green by its step, last row and column untouched."""
+        out = np.empty(self._shape, np.uint8)
+        self._ctx._check(lib().dcte_resizer_seams_u8(self._h, out.ctypes.data))
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().dcte_resizer_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+__all__ = ["Context", "Carver", "Resizer", "DcteError", "lib", "device_count", "LIB_PATH", "EXPORTS",
            "energy_window", "normalize_u8_host",
            "DCTE_LQR", "DCTE_PREVIEW", "DCTE_OPT_TIE_TAU", "DCTE_OPT_EXACT", "DCTE_OPT_FAIL_INJECT", "DCTE_OPT_PROFILE", "DCTE_OPT_PIN_HOST", "DCTE_OPT_TILE_H", "DCTE_OPT_DP_BANDWISE", "DCTE_OPT_DP_SPIN_LIMIT",
            "DCTE_NORM_LQR", "DCTE_NORM_PREVIEW"]

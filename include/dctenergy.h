@@ -47,7 +47,9 @@ extern "C" {
  * option id 8 to 9 (8 = the removed WIDE_BANDS, accepted as a no-op) -- a
  * caller built against version 1 that arms id 8 injects nothing; new entry
  * points dcte_energy_map2 and dcte_carver_create2; a dcte_carver keeps the
- * arithmetic mode (DCTE_OPT_EXACT, DCTE_OPT_TIE_TAU) it was created in. */
+ * arithmetic mode (DCTE_OPT_EXACT, DCTE_OPT_TIE_TAU) it was created in.
+ * Still 2: the seam visibility map (dcte_vmap_*_device, dcte_resizer_*) is
+ * additive -- new exports only, nothing existing changed. */
 #define DCTE_ABI_VERSION 2
 
 /* status codes */
@@ -307,6 +309,90 @@ int dcte_seam_find(dcte_ctx *ctx, const float *map, int w, int h, int *seam);
 int dcte_carve(dcte_ctx *ctx, const uint8_t *px, int w, int h, int bpp, size_t rowstride,
                int n, float edges, float textures, int semantics, int seams, int transposed,
                uint8_t *out, int *seam_cols);
+
+/* ---- seam visibility map: resize to any width, enlarge, "Seams" layer ----
+ * What liblqr keeps from its carve loop and the reference uses three times:
+ * render() enlarges with a positive seams_number (src/render.c:358-377), the
+ * interactive dialog carves once and then resizes to every slider position
+ * from the kept map without new energies (src/interface.c:131-135,648-670),
+ * and output_seams paints the map onto the layer (src/render.c:204-240,
+ * 373-384).
+ *
+ * Carved frame: W x H -- the frame as given, or its transpose when
+ * transposed = 1, exactly as in dcte_carve.
+ *
+ * Visibility map: vmap[y][x] (int32, W x H) = k + 1 if original pixel (x, y)
+ * is the one step k (0 .. depth-1) removed, 0 if it survives all `depth`
+ * steps [liblqr, unverified: the numbering].  Per row, from the step columns
+ * c_k = seams[k*H + y] that dcte_carve returns:
+ *     alive = [0 .. W-1]
+ *     for k in 0 .. depth-1:  c = clamp(c_k, 0, len(alive)-1)   (the clamp of
+ *         vmap[y][alive.pop(c)] = k + 1                 dcte_seam_carve_device)
+ * so every row holds each of 1 .. depth exactly once.
+ *
+ * Render at delta in [-depth, +depth]: output width W + delta.  Per row, for
+ * x = 0 .. W-1 with v = vmap[y][x]:
+ *   delta <= 0: emit pixel x iff v == 0 || v > -delta -- bit for bit the frame
+ *     dcte_carve(seams = -delta) returns (the first j steps of a depth-`depth`
+ *     carve are the j-step carve); delta == 0 is a copy;
+ *   delta > 0: if 0 < v <= delta first emit an inserted pixel, then pixel x;
+ *     the inserted pixel is, per channel (alpha included),
+ *     (px[max(x-1,0)][c] + px[x][c]) / 2 in integers, truncated [liblqr,
+ *     unverified: the enlargement rule].  One pass, hence delta <= depth < W.
+ *
+ * Seams image: a copy of the frame in the caller's orientation (h rows of w,
+ * the frame's own bpp) with every pixel with vis != 0, x < w-1 and y < h-1
+ * painted (the last column and row are the reference's loop bounds,
+ * src/render.c:222-223): bpp 3, 4: R = 0, G = (uint8)(255.0 * vis / depth) in
+ * double, truncated, B = 0, alpha untouched; bpp 1: the grey byte becomes that
+ * G (a deviation: the reference's 3-byte pixel on a grey drawable degenerates
+ * to 0).
+ *
+ * Device pieces (frames, maps and seams in HBM; stream-ordered, no sync):
+ * dcte_vmap_device: d_seams (depth * H ints, as dcte_carve's seam_cols, on the
+ *   device; may be NULL when depth == 0) -> d_vmap, row y at d_vmap +
+ *   y*vmap_stride ints, every entry written.  0 <= depth < W.
+ * dcte_vmap_render_device: W x H frame + its map -> the (W + delta) x H frame
+ *   d_out; bpp 1, 3 or 4; |delta| <= depth < W.  The sources (frame, map)
+ *   and the destination must not overlap (DCTE_EINVAL).
+ * dcte_vmap_seams_u8_device: w x h frame + a w x h map (both in the caller's
+ *   orientation) -> the w x h seams image d_out (another buffer). */
+int dcte_vmap_device(dcte_ctx *ctx, int device, const int *d_seams, int depth, int W, int H,
+                     int32_t *d_vmap, long long vmap_stride, void *stream);
+int dcte_vmap_render_device(dcte_ctx *ctx, int device, const void *d_px, long long rowstride,
+                            int W, int H, int bpp, const int32_t *d_vmap, long long vmap_stride,
+                            int depth, int delta, void *d_out, long long out_rowstride,
+                            void *stream);
+int dcte_vmap_seams_u8_device(dcte_ctx *ctx, int device, const void *d_px, long long rowstride,
+                              int w, int h, int bpp, const int32_t *d_vmap, long long vmap_stride,
+                              int depth, void *d_out, long long out_rowstride, void *stream);
+
+/* Host handle for the dialog's carve-once, render-many pattern: holds the
+ * original frame and its visibility map in HBM on the first device
+ * (W*H*(bpp + 4) bytes; renders go through the context's staging buffers).
+ *
+ * dcte_resizer_create: the loop of dcte_carve to `depth` seams (same
+ *   arguments, same seams, the same handling of a timed-out search), then the
+ *   map.  0 <= depth < W.  seam_cols: optional, as dcte_carve's.  All energy
+ *   arithmetic happens here, in the mode the context has at this moment
+ *   (DCTE_OPT_EXACT, DCTE_OPT_TIE_TAU); options set afterwards change nothing
+ *   for the resizer.
+ * dcte_resizer_render: the frame resized by delta, |delta| <= depth, dense
+ *   rows; transposed 0: h rows of (w + delta) pixels; 1: (h + delta) rows of
+ *   w, as dcte_carve lays out.
+ * dcte_resizer_vmap: the map in the caller's orientation, h rows of w
+ *   (transposed = 1: entry [y][x] belongs to carved-frame pixel (y, x)).
+ * dcte_resizer_seams_u8: the seams image, h x w x bpp.
+ * A failed call (DCTE_EINVAL, ...) leaves the resizer usable. */
+typedef struct dcte_resizer dcte_resizer;
+int dcte_resizer_create(dcte_ctx *ctx, const uint8_t *px, int w, int h, int bpp, size_t rowstride,
+                        int n, float edges, float textures, int semantics, int depth,
+                        int transposed, int *seam_cols, dcte_resizer **out);
+int dcte_resizer_render(dcte_resizer *r, int delta, uint8_t *out);
+int dcte_resizer_vmap(dcte_resizer *r, int32_t *vmap);
+int dcte_resizer_seams_u8(dcte_resizer *r, uint8_t *out);
+int dcte_resizer_depth(const dcte_resizer *r);
+void dcte_resizer_destroy(dcte_resizer *r);
 
 /* ---- device mirror of a liblqr carver -------------------
  * The update_emap hook of the plug-in: after the first
