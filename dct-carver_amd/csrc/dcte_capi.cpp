@@ -1,8 +1,9 @@
 // dcte_capi.cpp -- C ABI of libdctenergy_hip.so (declared in include/dctenergy.h).
 //
 // Context = a set of devices; per device: lazily created stream, staging
-// buffers for the host entry point, and per-stream refinement scratch
-// (counter + list) so calls on different streams never share it.
+// buffers for the host entry point, and per-stream scratch (refinement
+// counter + lists, seam DP buffers, min/max keys) so calls on different
+// streams never share it.
 #include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -73,7 +74,8 @@ struct Device {
     size_t out_cap = 0;
     std::map<hipStream_t, FixScratch> fix;
     std::map<hipStream_t, DpScratch> dp;
-    unsigned* d_keys = nullptr;    // min/max scratch (per device; stream-ordered)
+    std::map<hipStream_t, unsigned*> keys;   // dcte_minmax_device: {min, max} keys per stream
+    unsigned* d_keys = nullptr;    // min/max scratch of the host entry points (d.stream)
     float* d_minmax = nullptr;
     uint8_t* d_u8 = nullptr;       // u8 staging for the host entry points
     size_t u8_cap = 0;
@@ -1094,6 +1096,10 @@ void dcte_destroy(dcte_ctx* ctx)
             (void)hipStreamSynchronize(kv.first);
             if (kv.second.buf) (void)hipFree(kv.second.buf);
             if (kv.second.xbuf) (void)hipFree(kv.second.xbuf);
+        }
+        for (auto& kv : d.keys) {
+            (void)hipStreamSynchronize(kv.first);
+            if (kv.second) (void)hipFree(kv.second);
         }
         if (d.d_in) (void)hipFree(d.d_in);
         if (d.d_out) (void)hipFree(d.d_out);
@@ -2304,11 +2310,13 @@ int dcte_minmax_device(dcte_ctx* ctx, int device, const float* d_E, long long n,
     if (!ctx || device < 0 || device >= (int)ctx->devs.size() || !d_E || !d_minmax || n <= 0)
         return DCTE_EINVAL;
     Device& d = ctx->devs[device];
-    int rc = ensure_stream(ctx, d);
-    if (rc) return rc;
-    // per-stream key scratch would be needed for concurrent calls on several
-    // streams of one device; min/max calls are stream-ordered per device
-    DCTE_HIP(ctx, dcte::launch_minmax(d_E, n, d.d_keys, d_minmax, (hipStream_t)stream));
+    hipStream_t s = (hipStream_t)stream;
+    DCTE_HIP(ctx, hipSetDevice(d.id));
+    // key scratch per (device, stream), as for fix and dp: calls on different
+    // streams may overlap, and each launch resets and reduces into its keys
+    unsigned*& keys = d.keys[s];
+    if (!keys) DCTE_HIP(ctx, hipMalloc(&keys, 2 * sizeof(unsigned)));
+    DCTE_HIP(ctx, dcte::launch_minmax(d_E, n, keys, d_minmax, s));
     return DCTE_OK;
 }
 

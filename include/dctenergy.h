@@ -199,7 +199,24 @@ int dcte_energy_map2(dcte_ctx *ctx, const uint8_t *px, int w, int h, int bpp,
  *             every row the clamp reaches for [y0, y1)
  *   d_out     device pointer; row y (y0 <= y < y1) at d_out + (y-y0)*out_stride
  *   stream    hipStream_t (NULL = default stream) the work is ordered on
- * Calls on different streams may run concurrently (separate scratch). */
+ *
+ * Stream contract of EVERY dcte_*_device entry point (this one and all below:
+ * map, map2, seam carve, points, windows, seam find, vmap, render, seams,
+ * min/max, normalise):
+ *   - all of the call's work (kernels, memsets, refinement and DP launches) is
+ *     ordered on `stream` and on no other: it starts after what the caller
+ *     enqueued there before and ends before what the caller enqueues after;
+ *   - the call copies nothing to or from the host and does not wait on the
+ *     host, EXCEPT when scratch for that (device, stream) must be allocated or
+ *     grow (the first call on a stream, a larger frame, more points): freeing
+ *     the old buffer may wait for the device.  A repeated call of the same or
+ *     a smaller size only enqueues;
+ *   - every (device, stream) pair has scratch of its own (refinement lists,
+ *     DP buffers, min/max keys), so calls on different streams of one context
+ *     may overlap on the device;
+ *   - one context still serves one host thread at a time: the calls
+ *     themselves must not be made concurrently.
+ * dcte_destroy waits for the streams it holds scratch for before freeing it. */
 int dcte_energy_map_device(dcte_ctx *ctx, int device, const void *d_px,
                            long long rowstride, int w, int h, int bpp,
                            int in_row0, int in_rows, int y0, int y1, int n,
