@@ -173,10 +173,19 @@ bool valid_n(int n) { return n == 2 || n == 4 || n == 8 || n == 16; }
 
 // the refinement margin a call uses: the exact mode refines every pixel it
 // does not compute in fp64 outright (seam bands and points; every map call
-// goes to dcte_exact.hip's sliding kernels)
-double eff_tau(const dcte_ctx* ctx, int n)
+// goes to dcte_exact.hip's sliding kernels).  DCTE_LQR_ALPHA has no fp32
+// path: every value of it is fp64, whatever DCTE_OPT_EXACT and
+// DCTE_OPT_TIE_TAU say.
+double eff_tau(const dcte_ctx* ctx, int n, int sem)
 {
+    if (sem == DCTE_LQR_ALPHA) return 1.0;
     return ctx->exact ? 1.0 : ctx->tie_tau >= 0 ? ctx->tie_tau : default_tie_tau(n);
+}
+
+// a map call of this semantics goes to dcte_exact.hip's sliding kernels
+bool map_is_exact(const dcte_ctx* ctx, int n, int sem)
+{
+    return (ctx->exact || sem == DCTE_LQR_ALPHA) && dcte::exact_supported(n, sem);
 }
 
 // Runs a block of calls in a given arithmetic mode and restores the
@@ -203,7 +212,7 @@ struct ModeScope {
 // window offsets -hl .. +hr of a semantics
 void halo(int n, int sem, int& hl, int& hr)
 {
-    hl = sem == DCTE_LQR ? n / 2 - 1 : (n - 1) / 2 - 1;
+    hl = sem != DCTE_PREVIEW ? n / 2 - 1 : (n - 1) / 2 - 1;   // DCTE_LQR_ALPHA: liblqr's window
     hr = n - 1 - hl;
 }
 
@@ -220,6 +229,7 @@ bool valid_sem_bpp(int sem, int bpp)
 {
     if (sem == DCTE_LQR) return bpp == 1 || bpp == 3;
     if (sem == DCTE_PREVIEW) return bpp == 1 || bpp == 3 || bpp == 4;
+    if (sem == DCTE_LQR_ALPHA) return bpp == 4;
     return false;
 }
 
@@ -263,7 +273,7 @@ using dcte::small_twiddles;
 // 1 for the preview's u8 luma)
 double weight_scale(int n, int sem)
 {
-    return (sem == DCTE_LQR ? dcte::kLumaScale : 1.0) * (n >= 8 ? (double)n : 1.0);
+    return (sem != DCTE_PREVIEW ? dcte::kLumaScale : 1.0) * (n >= 8 ? (double)n : 1.0);
 }
 
 dcte::FixParams fix_params(const uint8_t* px, long long rowstride, int w, int h, int in_row0,
@@ -430,9 +440,9 @@ int run_device(dcte_ctx* ctx, Device& d, const void* d_px, long long rowstride, 
     // shorter than a tile is one tile of exactly its rows (same results, and
     // the refinement list below is sized for the rows that exist)
     const int rows_a = y1 - y0, rows_b = yb1 - yb0;
-    const bool exact = ctx->exact && dcte::exact_supported(n, sem);
-    if (exact) return run_exact(ctx, d, d_px, rowstride, w, h, bpp, in_row0, in_rows, y0, y1, yb0, yb1, n,
-                                edges, textures, sem, d_out, out_stride, s);
+    if (map_is_exact(ctx, n, sem))
+        return run_exact(ctx, d, d_px, rowstride, w, h, bpp, in_row0, in_rows, y0, y1, yb0, yb1, n, edges,
+                         textures, sem, d_out, out_stride, s);
     DCTE_HIP(ctx, hipSetDevice(d.id));
     int tile_h = ctx->tile_h;
     if (tile_h <= 0)
@@ -506,7 +516,7 @@ int run_device(dcte_ctx* ctx, Device& d, const void* d_px, long long rowstride, 
     p.out_stride = out_stride;
     p.we = (float)((double)edges / scale);
     p.wt = (float)((double)textures / scale);
-    p.tie_tau = (float)eff_tau(ctx, n);
+    p.tie_tau = (float)eff_tau(ctx, n, sem);
     p.edges = edges;
     p.textures = textures;
     p.fix_list = f->d_list;
@@ -556,7 +566,7 @@ int run_device(dcte_ctx* ctx, Device& d, const void* d_px, long long rowstride, 
     };
     if (injected(1)) return fail(hipErrorLaunchFailure, "launch_map (injected)");
     f->phase ^= 1u;   // the launch ran: the next one uses the counter it zeroed
-    if ((p.we != p.wt && eff_tau(ctx, n) > 0) || eff_tau(ctx, n) >= 1.0) {
+    if ((p.we != p.wt && eff_tau(ctx, n, sem) > 0) || eff_tau(ctx, n, sem) >= 1.0) {
         if ((e = dcte::launch_fix_tiles(n, bpp, sem, q, s)) != hipSuccess) return fail(e, "launch_fix_tiles");
         if (injected(2)) return fail(hipErrorLaunchFailure, "launch_fix_tiles (injected)");
     }
@@ -829,7 +839,7 @@ int ensure_pipe(dcte_ctx* ctx, Device& d, size_t nev)
 int reset_refined(dcte_ctx* ctx, Device& d, int w, int rows, int n, int sem)
 {
     FixScratch* f = nullptr;
-    if (!(ctx->exact && dcte::exact_supported(n, sem))) {
+    if (!map_is_exact(ctx, n, sem)) {
         int rc = ensure_fix(ctx, d, d.stream, (size_t)w * (size_t)rows, &f);
         if (rc) return rc;
     } else {
@@ -1245,13 +1255,13 @@ int dcte_seam_carve_device(dcte_ctx* ctx, int device, const void* d_px, long lon
     p.map_out_stride = map_out_stride;
     p.we = (float)((double)edges / scale);
     p.wt = (float)((double)textures / scale);
-    p.tie_tau = (float)eff_tau(ctx, n);
+    p.tie_tau = (float)eff_tau(ctx, n, semantics);
     p.fix_count = f->d_count;
     p.fix_list = f->d_list;
     p.fix_cap = (unsigned)f->cap;
     DCTE_HIP(ctx, hipMemsetAsync(f->d_count, 0, sizeof(unsigned), s));
     DCTE_HIP(ctx, dcte::launch_seam_carve(p, s));
-    if ((p.we != p.wt && eff_tau(ctx, n) > 0) || eff_tau(ctx, n) >= 1.0) {
+    if ((p.we != p.wt && eff_tau(ctx, n, semantics) > 0) || eff_tau(ctx, n, semantics) >= 1.0) {
         dcte::FixParams q = fix_params(p.px_out, out_rowstride, w - 1, h, 0, bpp, n, 0, semantics,
                                        d_map_out, map_out_stride, edges, textures, f);
         DCTE_HIP(ctx, dcte::launch_fix(q, s));
@@ -1292,13 +1302,13 @@ int dcte_energy_points_device(dcte_ctx* ctx, int device, const void* d_px, long 
     p.map_out = d_out;
     p.we = (float)((double)edges / scale);
     p.wt = (float)((double)textures / scale);
-    p.tie_tau = (float)eff_tau(ctx, n);
+    p.tie_tau = (float)eff_tau(ctx, n, semantics);
     p.fix_count = f->d_count;
     p.fix_list = f->d_list;
     p.fix_cap = (unsigned)f->cap;
     DCTE_HIP(ctx, hipMemsetAsync(f->d_count, 0, sizeof(unsigned), s));
     DCTE_HIP(ctx, dcte::launch_points(p, s));
-    if ((p.we != p.wt && eff_tau(ctx, n) > 0) || eff_tau(ctx, n) >= 1.0) {
+    if ((p.we != p.wt && eff_tau(ctx, n, semantics) > 0) || eff_tau(ctx, n, semantics) >= 1.0) {
         dcte::FixParams q = fix_params(p.px, rowstride, w, h, 0, bpp, n, 0, semantics, d_out, 0,
                                        edges, textures, f);
         q.pts = d_xy;

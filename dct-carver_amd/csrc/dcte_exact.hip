@@ -130,6 +130,9 @@ struct Frame {
 // liblqr luma tables (LQR_ER_LUMA [liblqr, unverified], as dcte_ref64.h's
 // luma): grey lut[v] = v / 255; RGB lut[c * 256 + v] = k_c * (v / 255), so
 // (lut[r] + lut[256 + g]) + lut[512 + b] is the reference's double
+// BPP = 4 is the RGBA carver of DCTE_LQR_ALPHA (the only liblqr-window use
+// of 4-byte pixels): a fourth table alut[v] = v / 255 at lut[768 + v], and the
+// RGB double above times alut[a] (dcte_ref64.h luma_alpha, the unverified rule)
 template <int BPP>
 __device__ __forceinline__ void fill_lut(double* lut, int tx, int nthreads)
 {
@@ -141,6 +144,7 @@ __device__ __forceinline__ void fill_lut(double* lut, int tx, int nthreads)
             lut[v] = 0.2126 * q;
             lut[256 + v] = 0.7152 * q;
             lut[512 + v] = 0.0722 * q;
+            if constexpr (BPP == 4) lut[768 + v] = q;   // alut: alpha / 255
         }
     }
 }
@@ -148,8 +152,15 @@ template <int BPP>
 __device__ __forceinline__ double luma_of(const double* lut, uint32_t wd)
 {
     if constexpr (BPP == 1) return lut[wd & 255u];
-    else return (lut[wd & 255u] + lut[256 + ((wd >> 8) & 255u)]) + lut[512 + ((wd >> 16) & 255u)];
+    else {
+        const double bright = (lut[wd & 255u] + lut[256 + ((wd >> 8) & 255u)]) + lut[512 + ((wd >> 16) & 255u)];
+        if constexpr (BPP == 4) return r64::luma_alpha(bright, lut[768 + (wd >> 24)]);
+        else return bright;
+    }
 }
+// doubles of the tables above
+template <int BPP>
+constexpr int kLutLen = BPP == 1 ? 256 : (BPP == 3 ? 768 : 1024);
 
 // first / one-past-last output row of tile row by (tile_row0 / tile_row1 of
 // dcte_kernels.h) in arithmetic: a select between two fields of the kernel
@@ -190,7 +201,7 @@ __global__ __launch_bounds__(kEx8T, DCTE_EX_MINW) void dcte_exact8(const MapPara
 {
     constexpr int N = 8, HL = 3, HR = 4, G = 8, T = kEx8T, LW = kEx8LW;
     constexpr int XH = LW - T;                        // halo columns past one per lane
-    __shared__ double lut[BPP == 1 ? 256 : 768];
+    __shared__ double lut[kLutLen<BPP>];
     __shared__ double lum[2][G][LW];
 
     const int tx = threadIdx.x;
@@ -461,7 +472,7 @@ template <int BPP>
 __global__ __launch_bounds__(kEx16T, DCTE_EX16_MINW) void dcte_exact16(const MapParams p)
 {
     constexpr int N = 16, HL = 7, HR = 8, G = kEx16G, LW = kEx16LW, T = kEx16T;
-    __shared__ double lut[BPP == 1 ? 256 : 768];
+    __shared__ double lut[kLutLen<BPP>];
     __shared__ double lum[G][LW];
     __shared__ unsigned long long pmax[G][64];      // max |C| after (1,0), as bits (atomic max)
     __shared__ double pe[G][3][64];                 // |C01|, max |C0,2..15|, |C10|
@@ -633,7 +644,7 @@ template <int N, int BPP>
 __global__ __launch_bounds__(kExST) void dcte_exact_small(const MapParams p)
 {
     constexpr int HL = N / 2 - 1, HR = N / 2, G = 8, OW = 64 - (N - 1);
-    __shared__ double lut[BPP == 1 ? 256 : 768];
+    __shared__ double lut[kLutLen<BPP>];
     __shared__ double vrow[kExST / 64][2][N][64];   // per wave, by row parity: V[k2][lane]
 
     const int tx = threadIdx.x, l = tx & 63, wv = tx >> 6;
@@ -1184,51 +1195,69 @@ int preview_blocks_per_cu(int n)
     return e == hipSuccess ? v : 0;
 }
 
+// liblqr-window kernels (BPP 4: the RGBA carver of kSemLqrAlpha)
+template <int BPP>
+int lqr_blocks_per_cu(int n)
+{
+    int v = 0;
+    hipError_t e = hipErrorInvalidValue;
+    if (n == 8) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, dcte_exact8<BPP>, kEx8T, 0);
+    else if (n == 16) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, dcte_exact16<BPP>, kEx16T, 0);
+    else if (n == 4) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, dcte_exact_small<4, BPP>, kExST, 0);
+    else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, dcte_exact_small<2, BPP>, kExST, 0);
+    return e == hipSuccess ? v : 0;
+}
+
+template <int BPP>
+hipError_t launch_lqr_exact(int n, const MapParams& p, hipStream_t s)
+{
+    if (n == 8) return launch_exact8<BPP>(p, s);
+    if (n == 16) return launch_exact16<BPP>(p, s);
+    if (n == 4) return launch_exact_small<4, BPP>(p, s);
+    if (n == 2) return launch_exact_small<2, BPP>(p, s);
+    return hipErrorInvalidValue;
+}
+
 }  // namespace
 
 // workgroups of the exact kernel for (n, bpp, sem) one CU holds at once; cached
 int exact_blocks_per_cu(int n, int bpp, int sem)
 {
-    static std::atomic<int> cache[2][4][3];
+    static std::atomic<int> cache[3][4][3];
     const int ni = n == 2 ? 0 : (n == 4 ? 1 : (n == 8 ? 2 : 3)), bi = bpp == 1 ? 0 : (bpp == 3 ? 1 : 2);
-    const int si = sem == kSemLqr ? 0 : 1;
+    const int si = sem == kSemLqr ? 0 : (sem == kSemPreview ? 1 : 2);
     int v = cache[si][ni][bi].load(std::memory_order_relaxed);
     if (v) return v;
-    hipError_t e = hipErrorInvalidValue;
-    if (si == 1) {
+    if (si == 1)
         v = bpp == 1 ? preview_blocks_per_cu<1>(n) : (bpp == 3 ? preview_blocks_per_cu<3>(n) : preview_blocks_per_cu<4>(n));
-        e = v > 0 ? hipSuccess : hipErrorInvalidValue;
-    } else if (n == 8) e = bpp == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, dcte_exact8<1>, kEx8T, 0)
-                                  : hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, dcte_exact8<3>, kEx8T, 0);
-    else if (n == 16) e = bpp == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, dcte_exact16<1>, kEx16T, 0)
-                                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, dcte_exact16<3>, kEx16T, 0);
-    else if (n == 4) e = bpp == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, dcte_exact_small<4, 1>, kExST, 0)
-                                  : hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, dcte_exact_small<4, 3>, kExST, 0);
-    else e = bpp == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, dcte_exact_small<2, 1>, kExST, 0)
-                      : hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, dcte_exact_small<2, 3>, kExST, 0);
-    if (e != hipSuccess || v <= 0) v = 1;
+    else if (si == 2)
+        v = lqr_blocks_per_cu<4>(n);
+    else
+        v = bpp == 1 ? lqr_blocks_per_cu<1>(n) : lqr_blocks_per_cu<3>(n);
+    if (v <= 0) v = 1;
     cache[si][ni][bi].store(v, std::memory_order_relaxed);
     return v;
 }
 
+// (kSemLqrAlpha runs the liblqr-window kernels, so it has their tile geometry)
 bool exact_supported(int n, int sem)
 {
-    return (sem == kSemLqr || sem == kSemPreview) && (n == 2 || n == 4 || n == 8 || n == 16);
+    return (sem == kSemLqr || sem == kSemPreview || sem == kSemLqrAlpha) && (n == 2 || n == 4 || n == 8 || n == 16);
 }
 int exact_tile_w(int n, int sem)
 {
-    if (sem != kSemLqr) return n == 8 ? kExPTW : (n == 16 ? kExP16TW : kEx8T);
+    if (sem == kSemPreview) return n == 8 ? kExPTW : (n == 16 ? kExP16TW : kEx8T);
     return n == 8 ? kEx8T : (n == 16 ? 64 : (kExST / 64) * (64 - (n - 1)));
 }
 int exact_default_tile_h(int n, int sem)
 {
-    if (sem != kSemLqr && n == 16) return 64;
-    return (sem != kSemLqr && n == 8) ? kExPTT : DCTE_EX_TILE_H;
+    if (sem == kSemPreview && n == 16) return 64;
+    return (sem == kSemPreview && n == 8) ? kExPTT : DCTE_EX_TILE_H;
 }
 int exact_max_tile_h(int n, int sem)
 {
-    if (sem != kSemLqr && n == 16) return 64;                  // a lane per output row
-    return (sem != kSemLqr && n == 8) ? kExPTT : (1 << 30);
+    if (sem == kSemPreview && n == 16) return 64;                  // a lane per output row
+    return (sem == kSemPreview && n == 8) ? kExPTT : (1 << 30);
 }
 
 hipError_t launch_map_exact(int n, int bpp, int sem, const MapParams& p, hipStream_t s)
@@ -1240,20 +1269,10 @@ hipError_t launch_map_exact(int n, int bpp, int sem, const MapParams& p, hipStre
         if (bpp == 4) return launch_preview_exact<4>(n, p, s);
         return hipErrorInvalidValue;
     }
+    if (sem == kSemLqrAlpha) return bpp == 4 ? launch_lqr_exact<4>(n, p, s) : hipErrorInvalidValue;
     if (sem != kSemLqr) return hipErrorInvalidValue;
-    if (n == 8) {
-        if (bpp == 1) return launch_exact8<1>(p, s);
-        if (bpp == 3) return launch_exact8<3>(p, s);
-    } else if (n == 16) {
-        if (bpp == 1) return launch_exact16<1>(p, s);
-        if (bpp == 3) return launch_exact16<3>(p, s);
-    } else if (n == 4) {
-        if (bpp == 1) return launch_exact_small<4, 1>(p, s);
-        if (bpp == 3) return launch_exact_small<4, 3>(p, s);
-    } else if (n == 2) {
-        if (bpp == 1) return launch_exact_small<2, 1>(p, s);
-        if (bpp == 3) return launch_exact_small<2, 3>(p, s);
-    }
+    if (bpp == 1) return launch_lqr_exact<1>(n, p, s);
+    if (bpp == 3) return launch_lqr_exact<3>(n, p, s);
     return hipErrorInvalidValue;
 }
 

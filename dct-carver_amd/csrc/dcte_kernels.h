@@ -98,7 +98,7 @@ struct FixParams {
     const uint8_t* px;
     long long rowstride;
     int w, h, in_row0, bpp, n, y0;
-    int sem;                 // kSemLqr / kSemPreview
+    int sem;                 // kSemLqr / kSemPreview / kSemLqrAlpha (bpp 4)
     float* out;
     long long out_stride;
     float edges, textures;
@@ -237,7 +237,7 @@ int dense_batch_entries(int n, int sem);   // entries per dense refinement batch
 // the exact map (dcte_exact.hip, DCTE_OPT_EXACT): the reference's fp64
 // arithmetic in a sliding window, no refinement launch
 hipError_t launch_map_exact(int n, int bpp, int sem, const MapParams& p, hipStream_t s);
-bool exact_supported(int n, int sem);   // (every N, both semantics since r05)
+bool exact_supported(int n, int sem);   // (every N, every semantics; kSemLqrAlpha has no other map)
 int exact_tile_w(int n, int sem);       // output columns per workgroup
 int exact_default_tile_h(int n, int sem);
 int exact_max_tile_h(int n, int sem);     // rows one workgroup can take (preview N = 8: its lanes)

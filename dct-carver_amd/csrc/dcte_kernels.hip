@@ -734,8 +734,9 @@ __device__ __forceinline__ Pix fix_pixel(const FixParams& p, unsigned k)
 }
 
 // window element (i, j) of pixel q: liblqr data[dx][dy] (i = column offset),
-// preview data[dy][dx]
-template <int N, int SEM>
+// preview data[dy][dx].  ALPHA (SEM = kSemLqr, bpp 4): the RGBA carver of
+// kSemLqrAlpha, liblqr's window on the alpha-weighted luma (r64::luma_alpha)
+template <int N, int SEM, bool ALPHA = false>
 __device__ __forceinline__ double fix_elem(const FixParams& p, const double* lut, const Pix& q,
                                            int i, int j)
 {
@@ -745,6 +746,8 @@ __device__ __forceinline__ double fix_elem(const FixParams& p, const double* lut
     const int yy = clampi(q.y + oy - HL, 0, p.h - 1);
     const uint8_t* px = p.px + (long long)(yy - p.in_row0) * p.rowstride + (long long)xx * p.bpp;
     if constexpr (SEM == kSemLqr) {
+        if constexpr (ALPHA)
+            return r64::luma_alpha(0.2126 * lut[px[0]] + 0.7152 * lut[px[1]] + 0.0722 * lut[px[2]], lut[px[3]]);
         if (p.bpp == 1) return lut[px[0]];
         return 0.2126 * lut[px[0]] + 0.7152 * lut[px[1]] + 0.0722 * lut[px[2]];
     } else {
@@ -860,7 +863,7 @@ __device__ __forceinline__ void refine16_group(double* d, int l, double& best, b
     lastmax_group<16>(v, l, best, edge);
 }
 
-template <int N, int SEM>
+template <int N, int SEM, bool ALPHA = false>
 __global__ __launch_bounds__(kFixThreads) void dcte_fix(const FixParams p)
 {
     __shared__ double lut[256];
@@ -879,7 +882,7 @@ __global__ __launch_bounds__(kFixThreads) void dcte_fix(const FixParams p)
 #pragma unroll
             for (int i = 0; i < N; i++)
 #pragma unroll
-                for (int j = 0; j < N; j++) d[i * N + j] = fix_elem<N, SEM>(p, lut, q, i, j);
+                for (int j = 0; j < N; j++) d[i * N + j] = fix_elem<N, SEM, ALPHA>(p, lut, q, i, j);
             double m;
             bool edge;
             refine_regs<N>(d, p.ct, m, edge);
@@ -900,7 +903,7 @@ __global__ __launch_bounds__(kFixThreads) void dcte_fix(const FixParams p)
             if (valid) {
                 q = fix_pixel(p, k);
 #pragma unroll
-                for (int t = 0; t < 16; t++) d[t * 16 + l] = fix_elem<16, SEM>(p, lut, q, t, l);
+                for (int t = 0; t < 16; t++) d[t * 16 + l] = fix_elem<16, SEM, ALPHA>(p, lut, q, t, l);
             }
             wave_sync_lds();
             double best;
@@ -2576,6 +2579,8 @@ static void launch_fix_n(const FixParams& p, hipStream_t s)
     blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
     if (p.sem == kSemLqr)
         hipLaunchKernelGGL((dcte_fix<N, kSemLqr>), dim3(blocks), dim3(kFixThreads), 0, s, p);
+    else if (p.sem == kSemLqrAlpha)
+        hipLaunchKernelGGL((dcte_fix<N, kSemLqr, true>), dim3(blocks), dim3(kFixThreads), 0, s, p);
     else
         hipLaunchKernelGGL((dcte_fix<N, kSemPreview>), dim3(blocks), dim3(kFixThreads), 0, s, p);
 }

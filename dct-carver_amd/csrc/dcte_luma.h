@@ -19,9 +19,13 @@
 
 namespace dcte {
 
-// energy semantics (DCTE_LQR / DCTE_PREVIEW in include/dctenergy.h)
+// energy semantics (DCTE_LQR / DCTE_PREVIEW / DCTE_LQR_ALPHA in
+// include/dctenergy.h).  kSemLqrAlpha is liblqr's window and scan on an RGBA
+// frame whose luma is weighted by alpha (dcte_ref64.h luma_alpha); it has no
+// integer-luma form, so only the fp64 paths take it.
 constexpr int kSemLqr = 0;
 constexpr int kSemPreview = 1;
+constexpr int kSemLqrAlpha = 2;
 
 // Preview semantics: convert_row_to_luminance (src/render.c:62-79) with
 // RGB2LUMINANCE (src/render.h:5), evaluated in double left to right (the TU

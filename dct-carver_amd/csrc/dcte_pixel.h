@@ -34,7 +34,8 @@ DCTE_HD float luma_biased(const uint8_t* p, int bpp, int sem)
     return (float)(L - kLumaBias);
 }
 
-constexpr DCTE_HD int halo_left(int n, int sem) { return sem == kSemLqr ? n / 2 - 1 : (n - 1) / 2 - 1; }
+// (kSemLqrAlpha shares liblqr's window)
+constexpr DCTE_HD int halo_left(int n, int sem) { return sem != kSemPreview ? n / 2 - 1 : (n - 1) / 2 - 1; }
 
 // (m_t, m_e) of pixel (x, y) of a w x h frame; `px` addresses global row
 // `row0` (rows the window clamp reaches must be readable).

@@ -245,5 +245,13 @@ DCTE_HD64 double luma(const uint8_t* p, int bpp)
     return 0.2126 * r + 0.7152 * g + 0.0722 * b;
 }
 
+// The alpha rule of DCTE_LQR_ALPHA [liblqr, unverified]: LQR_ER_LUMA's
+// reading of a 4-channel 8-bit carver (LQR_RGBA_IMAGE, alpha last) is the RGB
+// brightness above times alpha / 255, one double product.  `bright` is
+// luma(p, 3) of the pixel's colour channels, `a` its alpha byte over 255 (the
+// quotient (double)v / 255, or the same double from a 256-entry table).
+// Every fp64 path of this semantics forms the value here and nowhere else.
+DCTE_HD64 double luma_alpha(double bright, double a) { return bright * a; }
+
 }  // namespace r64
 }  // namespace dcte

@@ -193,6 +193,16 @@ __device__ __forceinline__ void emit_pixel(const SeamParams& p, float mt, float 
     }
 }
 
+// kSemLqrAlpha has no fp32 form (dcte_luma.h): its recomputed pixels skip the
+// fp32 passes and all go on the refinement list, which the launcher always
+// runs for this semantics (dcte_fix, fp64); the zero is overwritten there
+__device__ __forceinline__ void defer_pixel(const SeamParams& p, float* dst, unsigned fix_index)
+{
+    *dst = 0.0f;
+    const unsigned k = atomicAdd(p.fix_count, 1u);
+    if (k < p.fix_cap) p.fix_list[k] = fix_index;
+}
+
 // recomputed band: one wave per row of the new frame
 template <int N, int BPP, int SEM>
 __global__ __launch_bounds__(256) void dcte_seam_band(const SeamParams p)
@@ -200,16 +210,20 @@ __global__ __launch_bounds__(256) void dcte_seam_band(const SeamParams p)
     const int y = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (y >= p.h) return;
-    constexpr int HL = SEM == kSemLqr ? N / 2 - 1 : (N - 1) / 2 - 1, HR = N - 1 - HL;
+    constexpr int HL = halo_left(N, SEM), HR = N - 1 - HL;
     const int w1 = p.w - 1;
     int lo, hi;
     seam_span(p.seam, p.w, p.h, N, SEM, y, lo, hi);
     const int a = max(0, lo - HR), b = hi <= p.w - 2 ? min(w1 - 1, hi + HL - 1) : w1 - 1;
     for (int x = a + lane; x <= b; x += 64) {
-        float mt, me;
-        pixel_maxima<N>(p.px_out, p.out_rowstride, 0, w1, p.h, BPP, SEM, x, y, mt, me);
-        emit_pixel(p, mt, me, p.map_out + (long long)y * p.map_out_stride + x,
-                   (unsigned)(y * w1 + x));
+        float* const dst = p.map_out + (long long)y * p.map_out_stride + x;
+        if constexpr (SEM == kSemLqrAlpha) {
+            defer_pixel(p, dst, (unsigned)(y * w1 + x));
+        } else {
+            float mt, me;
+            pixel_maxima<N>(p.px_out, p.out_rowstride, 0, w1, p.h, BPP, SEM, x, y, mt, me);
+            emit_pixel(p, mt, me, dst, (unsigned)(y * w1 + x));
+        }
     }
 }
 
@@ -219,10 +233,14 @@ __global__ __launch_bounds__(256) void dcte_points(const SeamParams p)
 {
     const int k = blockIdx.x * 256 + threadIdx.x;
     if (k >= p.count) return;
-    const int x = clamp_px(p.pts[2 * k], 0, p.w - 1), y = clamp_px(p.pts[2 * k + 1], 0, p.h - 1);
-    float mt, me;
-    pixel_maxima<N>(p.px, p.rowstride, p.in_row0, p.w, p.h, BPP, SEM, x, y, mt, me);
-    emit_pixel(p, mt, me, p.map_out + k, (unsigned)k);
+    if constexpr (SEM == kSemLqrAlpha) {
+        defer_pixel(p, p.map_out + k, (unsigned)k);
+    } else {
+        const int x = clamp_px(p.pts[2 * k], 0, p.w - 1), y = clamp_px(p.pts[2 * k + 1], 0, p.h - 1);
+        float mt, me;
+        pixel_maxima<N>(p.px, p.rowstride, p.in_row0, p.w, p.h, BPP, SEM, x, y, mt, me);
+        emit_pixel(p, mt, me, p.map_out + k, (unsigned)k);
+    }
 }
 
 // Band of one carver step (dcte_carver_step): after seam s removed from a
@@ -264,6 +282,8 @@ hipError_t launch_band_gather(const BandParams& p, hipStream_t s)
         if ((p).sem == kSemLqr) {                                                               \
             if ((p).bpp == 1) { hipLaunchKernelGGL((KERNEL<N, 1, kSemLqr>), grid, block, 0, s, p); break; }     \
             if ((p).bpp == 3) { hipLaunchKernelGGL((KERNEL<N, 3, kSemLqr>), grid, block, 0, s, p); break; }     \
+        } else if ((p).sem == kSemLqrAlpha) {                                                   \
+            if ((p).bpp == 4) { hipLaunchKernelGGL((KERNEL<N, 4, kSemLqrAlpha>), grid, block, 0, s, p); break; } \
         } else {                                                                                \
             if ((p).bpp == 1) { hipLaunchKernelGGL((KERNEL<N, 1, kSemPreview>), grid, block, 0, s, p); break; } \
             if ((p).bpp == 3) { hipLaunchKernelGGL((KERNEL<N, 3, kSemPreview>), grid, block, 0, s, p); break; } \

@@ -29,6 +29,7 @@ DCTE_ENOTSUP = -6
 
 DCTE_LQR = 0
 DCTE_PREVIEW = 1
+DCTE_LQR_ALPHA = 2  # liblqr semantics on RGBA (bpp 4): luma * alpha / 255, always fp64
 DCTE_OPT_TIE_TAU = 1
 DCTE_OPT_PROFILE = 2
 DCTE_OPT_PIN_HOST = 3
@@ -765,5 +766,5 @@ class Resizer:
 
 __all__ = ["Context", "Carver", "Resizer", "DcteError", "lib", "device_count", "LIB_PATH", "EXPORTS",
            "energy_window", "normalize_u8_host",
-           "DCTE_LQR", "DCTE_PREVIEW", "DCTE_OPT_TIE_TAU", "DCTE_OPT_EXACT", "DCTE_OPT_FAIL_INJECT", "DCTE_OPT_PROFILE", "DCTE_OPT_PIN_HOST", "DCTE_OPT_TILE_H", "DCTE_OPT_DP_BANDWISE", "DCTE_OPT_DP_SPIN_LIMIT",
+           "DCTE_LQR", "DCTE_PREVIEW", "DCTE_LQR_ALPHA", "DCTE_OPT_TIE_TAU", "DCTE_OPT_EXACT", "DCTE_OPT_FAIL_INJECT", "DCTE_OPT_PROFILE", "DCTE_OPT_PIN_HOST", "DCTE_OPT_TILE_H", "DCTE_OPT_DP_BANDWISE", "DCTE_OPT_DP_SPIN_LIMIT",
            "DCTE_NORM_LQR", "DCTE_NORM_PREVIEW"]

@@ -103,10 +103,13 @@ int dcte_plugin_build_ex(dcte_map_cache *c, const uint8_t *px, int w, int h, int
             if (!c->hook_ok) release_hook(c);
         }
     }
-    /* no mirror (no hook, or it could not be set up): both maps from one
-     * upload, dcte_energy_map2 */
+    /* no mirror (no hook, or it could not be set up; always for an RGBA frame,
+     * which the hook does not mirror): both maps from one upload,
+     * dcte_energy_map2 -- an RGBA frame's under DCTE_LQR_ALPHA when the caller
+     * opted in (DCTE_PLUGIN_ALPHA), else DCTE_EINVAL as for any bpp 4 */
     if (st == DCTE_OK && !c->mirror)
-        st = dcte_energy_map2(ctx, px, w, h, bpp, rowstride, blocksize, edges, textures, DCTE_LQR,
+        st = dcte_energy_map2(ctx, px, w, h, bpp, rowstride, blocksize, edges, textures,
+                              (flags & DCTE_PLUGIN_ALPHA) && bpp == 4 ? DCTE_LQR_ALPHA : DCTE_LQR,
                               c->map, c->map_t);
     pthread_mutex_unlock(&g_ctx_lock);
     if (st != DCTE_OK) {

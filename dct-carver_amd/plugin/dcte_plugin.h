@@ -57,6 +57,14 @@ typedef struct {
  * later build or preview in the other mode (the dialog's preview, a second
  * carver, src/interface.c:116,524,662) does not change it. */
 #define DCTE_PLUGIN_EXACT 2u
+/* an RGBA layer (bpp 4) is mapped under DCTE_LQR_ALPHA: liblqr's luma times
+ * alpha / 255 [liblqr, unverified -- see dctenergy.h; opt in only once the
+ * rule has been checked against the liblqr the plug-in links], always in the
+ * reference's fp64 arithmetic.  Without the flag a bpp-4 build answers
+ * DCTE_EINVAL, every lookup misses and the plug-in runs its own body, as
+ * before.  The seam hook stays bpp 1 / 3: an RGBA build takes the maps-only
+ * branch.  No effect on bpp 1 / 3. */
+#define DCTE_PLUGIN_ALPHA 4u
 
 /* Build the map(s) for the frame handed to lqr_carver_new (src/render.c:312):
  * orientation 0 always, and the transposed frame's map too when

@@ -49,7 +49,9 @@ extern "C" {
  * points dcte_energy_map2 and dcte_carver_create2; a dcte_carver keeps the
  * arithmetic mode (DCTE_OPT_EXACT, DCTE_OPT_TIE_TAU) it was created in.
  * Still 2: the seam visibility map (dcte_vmap_*_device, dcte_resizer_*) is
- * additive -- new exports only, nothing existing changed. */
+ * additive -- new exports only, nothing existing changed.  Still 2:
+ * DCTE_LQR_ALPHA is a third semantics value; every (semantics, bpp) pair that
+ * was accepted or refused before is accepted or refused as before. */
 #define DCTE_ABI_VERSION 2
 
 /* status codes */
@@ -69,9 +71,30 @@ extern "C" {
  *              421-479): u8 luma RGB2LUMINANCE (src/render.h:5; grey = the
  *              byte), window -(c-1)..N-c with c = (N-1)/2 (src/dct.h:8-9),
  *              clamp to the region passed in; bpp 1, 3 or 4 (alpha ignored,
- *              as convert_row_to_luminance does) */
+ *              as convert_row_to_luminance does)
+ * DCTE_LQR_ALPHA  DCTE_LQR for an RGBA layer, bpp 4 ONLY (alpha = the last
+ *              channel; bpp 1, 2, 3 are DCTE_EINVAL, and DCTE_LQR itself keeps
+ *              refusing bpp 2 and 4).  liblqr's LQR_ER_LUMA reading of a
+ *              4-channel 8-bit carver (LQR_RGBA_IMAGE) is taken to be, in
+ *              double [liblqr, unverified]:
+ *                  bright = 0.2126 R/255 + 0.7152 G/255 + 0.0722 B/255
+ *                  value  = bright * (A/255)
+ *              with DCTE_LQR's window, transform and last-maximum scan.
+ *              Carving moves whole 4-byte pixels; enlargement averages alpha
+ *              like any channel.  Opt-in: nothing takes this value unless the
+ *              caller passes it.
+ *              There is NO fp32 path for it (the fp32 map rests on an exact
+ *              integer luma below 2^24, dcte_luma.h; luma x alpha reaches
+ *              3.3e8): every energy -- maps, seam-band updates, points,
+ *              carves, resizers, u8 images -- is computed in the reference's
+ *              fp64 operation order, bit-identical to the rule above, which
+ *              is more than the <= 1e-5 promise.  DCTE_OPT_EXACT and
+ *              DCTE_OPT_TIE_TAU do not change its results, and
+ *              dcte_last_refined reports 0 after a map call of it.
+ *              dcte_carver_* has no semantics argument and stays bpp 1 / 3. */
 #define DCTE_LQR 0
 #define DCTE_PREVIEW 1
+#define DCTE_LQR_ALPHA 2
 
 /* options for dcte_set_option */
 #define DCTE_OPT_TIE_TAU 1 /* relative edge/texture margin refined in fp64
@@ -126,7 +149,8 @@ extern "C" {
                                window kernel, so liblqr's DP on it carves the
                                reference's seams -- every N, both semantics
                                (the preview's transposed window has kernels of
-                               its own).  Seam-band updates and point energies are then
+                               its own; DCTE_LQR_ALPHA is always computed this
+                               way, with or without the option).  Seam-band updates and point energies are then
                                refined in fp64 too.  0 = the fp32 map with the
                                tie refinement (default; <= 1e-5 relative). */
 
@@ -166,7 +190,7 @@ int dcte_set_option(dcte_ctx *ctx, int option, double value);
  *             lqr_carver_new, src/render.c:159-173,312)
  *   n         blocksize N (2, 4, 8, 16)
  *   edges, textures   weights (PlugInVals, src/main.h:12-22)
- *   semantics DCTE_LQR or DCTE_PREVIEW
+ *   semantics DCTE_LQR, DCTE_PREVIEW or DCTE_LQR_ALPHA (bpp 4)
  *   transposed 1 = the map of the transposed frame (what the callback returns
  *             once liblqr has transposed the carver for a vertical resize);
  *             out then holds w rows of h floats
